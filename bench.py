@@ -20,7 +20,12 @@ time and keeps a random sample of delivered seqs; p50/p99 of
 (receive time - submission timestamp) are computed from those headers.
 
 Usage (driver contract):
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+A plain run sets up, warms up, times the K steps and prints the result
+line. --full additionally runs the per-message latency phase and the
+GPU-busy sampler (p50/p99/n_latency_samples/gpu_busy_pct in the result
+line). --dump-outputs DIR writes what the last timed step delivered as
+DIR/<name>.npy (see dump_outputs below).
 For N>1 the driver launches via torch.distributed.run; ranks read
 RANK/LOCAL_RANK/WORLD_SIZE from the env. Scaling is weak: 1024 agents and
 the same message load per GPU.
@@ -79,6 +84,47 @@ def build_batches(rng, n_batches, batch, agents_global, rank, world,
     return batches, local_agents
 
 
+def dump_outputs(out_dir, engine, counts, seqs, seq_base, payload_bytes,
+                 rank, world):
+    """Write what the last timed step delivered as DIR/<name>.npy.
+
+    counts       float32 [n_agents]   messages delivered to each polled agent
+    seq_offsets  float64 [n_delivered] delivered seqs in agent order, relative
+                                       to the first seq the step enqueued (the
+                                       absolute base depends on how many
+                                       warmup ticks ran)
+    sample_index float64 [k]          positions in seq_offsets of a fixed,
+                                       seeded sample (k <= 4096)
+    headers      float32 [k, 4]       sender, receiver, priority, payload_len
+                                       of the sampled messages
+    payloads     float32 [k, payload] their payload bytes
+    """
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    sfx = f"_rank{rank}" if world > 1 else ""
+    counts = np.asarray(counts, dtype=np.int64)
+    seqs = np.asarray(seqs, dtype=np.uint64)
+    np.save(out / f"counts{sfx}.npy", counts.astype(np.float32))
+    np.save(out / f"seq_offsets{sfx}.npy",
+            seqs.astype(np.float64) - float(seq_base))
+    k = min(4096, len(seqs))
+    idx = np.sort(np.random.default_rng(0).choice(len(seqs), k, replace=False))
+    hdr_out = np.zeros((k, 4), dtype=np.float32)
+    pay_out = np.zeros((k, payload_bytes), dtype=np.float32)
+    if k:
+        hdrs, pays = engine.fetch(seqs[idx].copy())
+        for c, name in enumerate(
+            ("sender", "receiver", "priority", "payload_len")
+        ):
+            hdr_out[:, c] = hdrs[name]
+        for r, pay in enumerate(pays):
+            b = np.frombuffer(pay, dtype=np.uint8)[:payload_bytes]
+            pay_out[r, : len(b)] = b
+    np.save(out / f"sample_index{sfx}.npy", idx.astype(np.float64))
+    np.save(out / f"headers{sfx}.npy", hdr_out)
+    np.save(out / f"payloads{sfx}.npy", pay_out)
+
+
 def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -102,6 +148,12 @@ def main() -> int:
     ap.add_argument("--graph", action="store_true",
                     help="use the hipGraph-captured tick (measured neutral "
                          "at large batches, slower at small — default off)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed "
+                         "step delivered as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the per-message latency phase and the "
+                         "GPU-busy sampler (a plain run only times the steps)")
     args = ap.parse_args()
 
     import torch
@@ -207,6 +259,9 @@ def main() -> int:
     # costs ~6% throughput, which must not contaminate the timed
     # region); the latencies are still real per-message measurements.
     sampling = {"on": False}
+    # --dump-outputs: the last timed step keeps its counts and delivered
+    # seqs (dense [na, K] layouts are compacted) for dump_outputs()
+    capture = {"on": False, "counts": None, "seqs": None}
     lat_deltas: list = []  # per-message (t_recv - submission) seconds
 
     def keep_sample(t_recv: float, seqs, counts=None, K=None) -> None:
@@ -283,6 +338,9 @@ def main() -> int:
                 engine.fetch(seqs)
         if sampling["on"] and ndel:
             keep_sample(time.time(), seqs)
+        if capture["on"]:
+            capture["counts"] = np.asarray(counts, dtype=np.int64)
+            capture["seqs"] = np.asarray(seqs, dtype=np.uint64).copy()
         sent_total += sent_local
         recv_total += ndel
         return ndel
@@ -353,7 +411,7 @@ def main() -> int:
                 # upload batch i+1 on the H2D stream: overlaps batch i's
                 # kernels and the delivery D2H (full-duplex PCIe)
                 _prefetch(1 - cur, i + 1)
-                want_seqs = args.bcast_frac > 0 or sampled
+                want_seqs = args.bcast_frac > 0 or sampled or capture["on"]
                 counts, seqs = q.receive_many(
                     local_agents32, recv_K, bool(args.priority),
                     return_seqs=want_seqs,
@@ -384,6 +442,15 @@ def main() -> int:
                 engine.delivery_sync()
                 keep_sample(time.time(), seqs,
                             counts=counts_dense, K=recv_K)
+            if capture["on"]:
+                c64 = counts.astype(np.int64)
+                mat = np.asarray(seqs, dtype=np.uint64).reshape(
+                    len(local_agents32), recv_K
+                )
+                capture["counts"] = c64
+                capture["seqs"] = mat[
+                    np.arange(recv_K)[None, :] < c64[:, None]
+                ]
             sent_total += n_staged
             recv_total += ndel
             _cur[0] = 1 - cur
@@ -416,6 +483,10 @@ def main() -> int:
         )
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         extra = int(t.item())
+    # the floor makes the warmup count timing-dependent: pad it to a
+    # multiple of the batch rotation so timed step j always sends batch
+    # j % len(batches) (same arguments -> same inputs, run to run)
+    extra += -(it + extra) % len(batches)
     for _ in range(extra):
         step(it)
         it += 1
@@ -429,7 +500,7 @@ def main() -> int:
     # sysfs gpu_busy_percent every 50 ms on a daemon thread
     busy_samples: list = []
     stop_busy = False
-    if have_gpu and rank == 0:
+    if args.full and have_gpu and rank == 0:
         import glob as _glob
         import threading as _threading
 
@@ -451,20 +522,33 @@ def main() -> int:
     barrier_sync()
     t0 = time.perf_counter()
     step_times = []
-    for _ in range(args.steps):
+    for j in range(args.steps):
+        capture["on"] = bool(args.dump_outputs) and j == args.steps - 1
         s = time.perf_counter()
+        sent_before = sent_total
         step(it)
         it += 1
         step_times.append(time.perf_counter() - s)
     barrier_sync()
     t1 = time.perf_counter()
     stop_busy = True
+    capture["on"] = False
 
-    # latency phase: same steady state, sampling on, UNTIMED (every
-    # rank runs the same count — the distributed step has collectives);
-    # capped at 64 steps (8k samples) so soak-length runs don't spend
+    if args.dump_outputs and capture["counts"] is not None:
+        sync = getattr(engine, "delivery_sync", None)
+        if sync is not None:
+            sync()  # the last delivery D2H shares the fetch staging buffer
+        dump_outputs(
+            args.dump_outputs, engine, capture["counts"], capture["seqs"],
+            engine.total_messages() - (sent_total - sent_before),
+            args.payload, rank, world,
+        )
+
+    # latency phase (--full only): same steady state, sampling on,
+    # UNTIMED (every rank runs the same count — the distributed step has
+    # collectives); capped at 128 steps so soak-length runs don't spend
     # minutes sampling
-    lat_steps = max(8, min(args.steps // 2, 128))
+    lat_steps = max(8, min(args.steps // 2, 128)) if args.full else 0
     # Alternate sampled/unsampled steps: a sampled step's bookkeeping
     # (drain + header fetch) runs AFTER its own receive stamp but ages
     # the NEXT step's messages — with every step sampled that observer
@@ -473,7 +557,7 @@ def main() -> int:
     # unsampled flush steps first drain the batch that was prefetched
     # (and stamped) before the end-of-loop barrier.
     lat_sent = lat_recv = 0
-    for _ in range(2):
+    for _ in range(2 if args.full else 0):
         before_s, before_r = sent_total, recv_total
         step(it)
         it += 1
@@ -490,7 +574,7 @@ def main() -> int:
         lat_sent += sent_total - before_s
         lat_recv += recv_total - before_r
     sampling["on"] = False
-    if args.dump_steps and rank == 0:
+    if args.dump_steps and args.full and rank == 0:
         print("phase_times_ms:",
               [round(t * 1000, 3) for t in phase_times])
     sent_total -= lat_sent  # latency phase is outside the timed totals
@@ -558,17 +642,6 @@ def main() -> int:
             "vs_baseline": None,  # reference publishes no numbers
             "dtype": "uint8",
             "data": "synthetic",
-            "p50_latency_ms": round(p50_ms, 3),
-            "p99_latency_ms": round(p99_ms, 3),
-            "n_latency_samples": n_lat,
-            # None when sysfs gpu_busy_percent is absent or pinned at 0
-            # (non-functional in this pool's containers — the rocprofv3
-            # kernel evidence in profiles/ covers utilization instead)
-            "gpu_busy_pct": (
-                round(float(np.mean(busy_samples)), 1)
-                if busy_samples and max(busy_samples) > 0
-                else None
-            ),
             "config": {
                 "model": "gpu-mpmc-ring-queue",
                 "global_batch": args.batch * world,
@@ -582,6 +655,18 @@ def main() -> int:
                 "payload_gather_d2h": not args.no_gather,
             },
         }
+        if args.full:
+            out["p50_latency_ms"] = round(p50_ms, 3)
+            out["p99_latency_ms"] = round(p99_ms, 3)
+            out["n_latency_samples"] = n_lat
+            # None when sysfs gpu_busy_percent is absent or reads 0
+            # throughout (the kernel evidence in profiles/ covers
+            # utilization instead)
+            out["gpu_busy_pct"] = (
+                round(float(np.mean(busy_samples)), 1)
+                if busy_samples and max(busy_samples) > 0
+                else None
+            )
         print(json.dumps(out))
 
     engine.close()

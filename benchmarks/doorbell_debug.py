@@ -1,5 +1,6 @@
 import sys, struct, time
-sys.path.insert(0, "/root/repo")
+from pathlib import Path
+sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
 from swarmdb_amd import _swarmq
 
 db = _swarmq.DoorbellQueue(slot_bytes=256, sub_cap=256, n_agents=4,

@@ -587,6 +587,7 @@ def main() -> int:
             "--agents", str(max(1, 4096 // world)),
             "--steps", "30",
             "--warmup", "5",
+            "--full",  # config 4 reports the p50/p99 latency too
         ]
         import bench
 

@@ -1,5 +1,6 @@
 import sys, time, json
-sys.path.insert(0, "/root/repo")
+from pathlib import Path
+sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
 import numpy as np
 from swarmdb_amd import QueueConfig
 from swarmdb_amd.runtime.gpu_engine import GpuEngine

@@ -337,7 +337,7 @@ def test_bench_distributed_gloo_gpu_engines(tmp_path):
             "--nnodes=1", "--nproc-per-node=2",
             "--master-addr=127.0.0.1", "--master-port=29534",
             str(REPO / "bench.py"), "--gpus", "2", "--steps", "4",
-            "--warmup", "1", "--agents", "64", "--batch", "512",
+            "--warmup", "1", "--agents", "64", "--batch", "512", "--full",
         ],
         capture_output=True, text=True, timeout=420, env=env,
         cwd=str(REPO),
