@@ -11,9 +11,11 @@
                    with --agents 4096/N)
   5 loadbalancer   8 mock backends, least-loaded dispatch + JSON history
                    spill
+ 10 p2p-device     config 2's traffic, delivered into HBM tensors and
+                   acked from the device (no payload or seq D2H)
 
 Usage:
-  python -m benchmarks.run --config {1,2,3,5} [--seconds S]
+  python -m benchmarks.run --config {1,2,3,5,10} [--seconds S]
   python -m torch.distributed.run --nproc-per-node N benchmarks/run.py --config 4
 
 Each config prints one JSON line:
@@ -162,6 +164,53 @@ def config2_p2p_gpu(seconds: float) -> None:
     _emit(2, "p2p-gpu-1kb", n, elapsed, float(np.median(lat) * 1000),
           {"express_p50_us": round(express_p50_us, 1),
            "express_p99_us": round(express_p99_us, 1)})
+
+
+def config10_device_delivery(seconds: float) -> None:
+    """Config 2's traffic (2 agents point-to-point, 4096 x 1 KB per tick)
+    delivered device-resident: each tick is enqueue_batch ->
+    receive_to_device (payloads, headers and seqs stay in HBM tensors,
+    only the counts cross PCIe) -> ack_device on the device seq tensor.
+    The delivery buffers are allocated once and reused, as config 2
+    reuses its pinned staging."""
+    import torch  # noqa: F401  (before GpuEngine: torch's HIP runtime first)
+
+    from swarmdb_amd.runtime.gpu_engine import GpuEngine
+
+    cfg = QueueConfig(use_gpu=True, auto_save=False, max_agents=64,
+                      num_slots=1 << 20, staging_batch=16384)
+    eng = GpuEngine(cfg)
+    eng.register_agent(0)
+    eng.register_agent(1)
+    rng = np.random.default_rng(0)
+    batch = 4096  # one dequeue window, as in config 2
+    recs, payload = _make_batch(rng, batch, np.array([0]), np.array([1]), 1024)
+    agents = np.array([1], dtype=np.uint32)
+    lat = []
+    n = 0
+    d = None
+    for _ in range(3):  # warmup
+        eng.enqueue_batch(recs, payload)
+        d = eng.receive_to_device(agents, batch, max_payload=1024, out=d)
+        eng.ack_device(d.seqs, n=d.total)
+    t0 = time.perf_counter()
+    while time.perf_counter() - t0 < seconds:
+        s = time.perf_counter()
+        eng.enqueue_batch(recs, payload)
+        d = eng.receive_to_device(agents, batch, max_payload=1024, out=d)
+        eng.ack_device(d.seqs, n=d.total)
+        lat.append(time.perf_counter() - s)
+        assert d.total == batch, "device tick failed to drain"
+        n += d.total
+    elapsed = time.perf_counter() - t0
+    # spot-check the last tick's bytes (outside the timed region)
+    h = d.to_host()
+    src = np.frombuffer(payload, dtype=np.uint8)[: batch * 1024]
+    assert np.array_equal(h.payload.reshape(-1), src), "payload mismatch"
+    eng.close()
+    _emit(10, "p2p-gpu-1kb-device-resident", n, elapsed,
+          float(np.median(lat) * 1000),
+          {"delivery": "device", "stride": d.stride})
 
 
 def config3_group_fanout(seconds: float) -> None:
@@ -570,7 +619,7 @@ def config5_loadbalancer(seconds: float) -> None:
 def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", type=int, required=True,
-                    choices=[1, 2, 3, 4, 5, 6, 7, 8, 9])
+                    choices=[1, 2, 3, 4, 5, 6, 7, 8, 9, 10])
     ap.add_argument("--seconds", type=float, default=5.0)
     args = ap.parse_args()
     if args.config == 1:
@@ -602,6 +651,8 @@ def main() -> int:
         config8_hbm_scale(args.seconds)
     elif args.config == 9:
         config9_distributed_service(args.seconds)
+    elif args.config == 10:
+        config10_device_delivery(args.seconds)
     return 0
 
 

@@ -428,6 +428,133 @@ __global__ void k_gather_outbuf(const u64 *__restrict__ out_seqs,
     dst[c] = src[c];
 }
 
+// Device-resident delivery, step 1: exclusive prefix sum of the dequeue
+// counts, offsets[0..n] with offsets[n] = total. One 256-thread
+// workgroup: a 64-lane shuffle scan per wave, the four wave totals
+// combined through LDS, tiles of 256 chained by a running total (every
+// thread keeps the same copy of it, so no broadcast is needed). Replaces
+// the host-side cumsum of deliver_outbuf — the counts never leave HBM.
+__global__ void __launch_bounds__(256)
+    k_scan_counts(const u32 *__restrict__ counts, int n,
+                  u32 *__restrict__ offsets) {
+  // dynamic LDS: the four wave totals of the current tile
+  extern __shared__ __attribute__((aligned(16))) u32 scan_wave_tot[];
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+  u32 running = 0;
+  for (int base = 0; base < n; base += 256) {
+    const int i = base + (int)threadIdx.x;
+    const u32 c = (i < n) ? counts[i] : 0u;
+    u32 v = c; // inclusive scan within the wave
+    for (int d = 1; d < 64; d <<= 1) {
+      const u32 t = __shfl_up(v, d, 64);
+      if (lane >= d)
+        v += t;
+    }
+    if (lane == 63)
+      scan_wave_tot[wave] = v;
+    __syncthreads();
+    u32 before = 0, tile = 0;
+    for (int w = 0; w < 4; ++w) {
+      const u32 t = scan_wave_tot[w];
+      if (w < wave)
+        before += t;
+      tile += t;
+    }
+    if (i < n)
+      offsets[i] = running + before + v - c;
+    running += tile;
+    __syncthreads(); // the next tile overwrites the wave totals
+  }
+  if (threadIdx.x == 0)
+    offsets[n] = running;
+}
+
+// Byte mask of the 32-bit word that starts at byte `first` of a 16-B
+// chunk whose first `rem` bytes are live (little-endian).
+__device__ inline u32 tail_mask(u32 rem, u32 first) {
+  if (rem >= first + 4)
+    return ~0u;
+  if (rem <= first)
+    return 0u;
+  return (1u << (8 * (rem - first))) - 1u;
+}
+
+// Device-resident delivery, step 2: blockIdx.x is the polled agent (the
+// k_receive grid), and the four waves of a 256-thread workgroup stride
+// over that agent's delivered messages, writing packed rows
+// r = offsets[b] + i into caller-provided device buffers. With many
+// agents and small counts one workgroup per agent has no idle waves;
+// with few agents and a deep inbox (one agent draining 4096 x 1 KB
+// through a single workgroup: a 1.9 ms tick, against 0.59 ms now) the
+// host adds gridDim.y workgroups per agent that interleave over the
+// same messages, and the ones past the agent's count exit at once (see
+// profiles/device_delivery.md). Unlike the D2H gathers above,
+// every row is fully defined: the last 16-B chunk is masked at
+// payload_len (a slot reused after ring wrap still holds the previous
+// occupant's bytes there) and the rest of the row is zero-filled. The
+// header is rebased so payload_off indexes the delivered payload tensor.
+__global__ void __launch_bounds__(256)
+    k_deliver_device(const u64 *__restrict__ out_seqs,
+                     const u32 *__restrict__ counts,
+                     const u32 *__restrict__ offsets, int n_agents, int K,
+                     const Rec *__restrict__ hdr,
+                     const u8 *__restrict__ payload,
+                     u8 *__restrict__ out_pay, uint4 *__restrict__ out_hdr,
+                     long long *__restrict__ out_seq,
+                     int *__restrict__ out_len, int *__restrict__ out_row,
+                     u32 stride, QueueGeom g) {
+  const int b = blockIdx.x;
+  if (b >= n_agents)
+    return;
+  const u32 lane = threadIdx.x & 63;
+  const u32 wave = threadIdx.x >> 6;
+  const u32 cnt = counts[b];
+  const u32 off = offsets[b];
+  const u32 row_chunks = stride >> 4;
+  for (u32 i = blockIdx.y * 4 + wave; i < cnt; i += 4 * gridDim.y) {
+    const u64 seq = out_seqs[(u64)b * (u32)K + i];
+    const Rec h = hdr[seq % g.num_slots];
+    const u64 r = (u64)off + i;
+    const u32 plen = h.payload_len < stride ? h.payload_len : stride;
+    const u32 full = plen >> 4; // whole 16-B chunks
+    const u32 rem = plen & 15u; // live bytes of the chunk after them
+    const uint4 *src =
+        reinterpret_cast<const uint4 *>(payload + h.payload_off);
+    uint4 *dst = reinterpret_cast<uint4 *>(out_pay + r * stride);
+    for (u32 c = lane; c < row_chunks; c += 64) {
+      uint4 v = make_uint4(0u, 0u, 0u, 0u);
+      if (c < full) {
+        v = src[c];
+      } else if (c == full && rem) {
+        v = src[c];
+        // keep bytes [0, rem) of the chunk: word w holds bytes 4w..4w+3
+        v.x &= tail_mask(rem, 0);
+        v.y &= tail_mask(rem, 4);
+        v.z &= tail_mask(rem, 8);
+        v.w &= tail_mask(rem, 12);
+      }
+      dst[c] = v;
+    }
+    if (lane == 0) {
+      Rec hh = h;
+      hh.payload_off = r * stride;
+      uint4 hv[3];
+      __builtin_memcpy(hv, &hh, sizeof(Rec));
+      uint4 *oh = out_hdr + r * 3;
+      oh[0] = hv[0];
+      oh[1] = hv[1];
+      oh[2] = hv[2];
+    } else if (lane == 1) {
+      out_seq[r] = (long long)seq;
+    } else if (lane == 2) {
+      out_len[r] = (int)plen;
+    } else if (lane == 3) {
+      out_row[r] = b;
+    }
+  }
+}
+
 // Gather message contents for the host (receive payload delivery, fetch,
 // history spill): one wave per message, dense slot_bytes-strided output.
 __global__ void k_gather(const u64 *__restrict__ seqs, int n,
@@ -758,6 +885,34 @@ __global__ void k_set_statuses(const u64 *__restrict__ seqs,
       atomicAdd(&by_status[old], (ull)(-1ll));
     if (ns < N_STATUS)
       atomicAdd(&by_status[ns], 1ull);
+  }
+}
+
+// Device-side ack: the consumer hands back the int64 seq tensor of a
+// device-resident delivery and the seqs are read straight from its
+// pointer. An evicted seq is skipped (its slot belongs to a newer
+// message), so is one never assigned, and a tombstone is never
+// resurrected. A broadcast delivered to several agents shows up more
+// than once; the exchange makes the counter move exactly once.
+__global__ void k_ack_device(const long long *__restrict__ seqs, int n,
+                             u32 new_status, u64 evict_base, u64 count,
+                             u32 *__restrict__ status,
+                             ull *__restrict__ by_status, QueueGeom g) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n)
+    return;
+  const u64 s = (u64)seqs[i];
+  if (s < evict_base || s >= count)
+    return;
+  const u32 slot = (u32)(s % g.num_slots);
+  if (status[slot] == ST_DELETED)
+    return;
+  const u32 old = atomicExch(&status[slot], new_status);
+  if (old != new_status) {
+    if (old < N_STATUS)
+      atomicAdd(&by_status[old], (ull)(-1ll));
+    if (new_status < N_STATUS)
+      atomicAdd(&by_status[new_status], 1ull);
   }
 }
 
@@ -1466,6 +1621,112 @@ public:
     return (u64)total * stride;
   }
 
+  // Device-resident delivery: dequeue + device scan + packed delivery
+  // into CALLER-provided device buffers (torch tensors' data_ptr()), all
+  // on stream_. Only the per-agent counts (na * 4 B) come back over
+  // PCIe. Row r = offsets[b] + i gets payload[r*stride..), headers[r]
+  // (48 B, payload_off rebased to r*stride), seqs[r] (i64), lengths[r]
+  // and agent_row[r] (i32); offsets is u32[na + 1]. Every check runs
+  // BEFORE the dequeue kernel, which advances cursors: a refused call
+  // leaves the queue untouched. Synchronizes, so the buffers are safe on
+  // any stream after return.
+  py::array_t<u32> receive_to_device(py::array_t<u32> agents,
+                                     int max_per_agent, bool priority,
+                                     u32 stride, uintptr_t payload_ptr,
+                                     uintptr_t headers_ptr, uintptr_t seqs_ptr,
+                                     uintptr_t lengths_ptr,
+                                     uintptr_t agent_row_ptr,
+                                     uintptr_t offsets_ptr,
+                                     size_t capacity_rows) {
+    const int na = (int)agents.size();
+    if (max_per_agent < 0)
+      throw std::invalid_argument("max_per_agent must be >= 0");
+    if ((u32)na > g_.max_agents)
+      throw std::invalid_argument("more polled agents than max_agents");
+    const size_t rows = (size_t)na * (size_t)max_per_agent;
+    if (rows > out_pool_)
+      throw std::invalid_argument("receive batch exceeds output pool");
+    if (capacity_rows < rows)
+      throw std::invalid_argument(
+          "delivery buffers hold fewer than agents * max_per_agent rows");
+    if (stride < 16 || stride > g_.slot_bytes || stride % 16 != 0)
+      throw std::invalid_argument(
+          "stride must be a multiple of 16 in 16..slot_bytes");
+    if (!offsets_ptr || offsets_ptr % 4)
+      throw std::invalid_argument("offsets buffer missing or misaligned");
+    if (rows && (!payload_ptr || !headers_ptr || !seqs_ptr || !lengths_ptr ||
+                 !agent_row_ptr))
+      throw std::invalid_argument("delivery buffer pointer is null");
+    if (payload_ptr % 16 || headers_ptr % 16 || seqs_ptr % 8 ||
+        lengths_ptr % 4 || agent_row_ptr % 4)
+      throw std::invalid_argument("delivery buffer is misaligned");
+    const u32 *ap = agents.data();
+    for (int i = 0; i < na; ++i)
+      if (ap[i] >= g_.max_agents)
+        throw std::invalid_argument("agent index out of range");
+    py::array_t<u32> counts(na);
+    if (na == 0)
+      return counts;
+    {
+      py::gil_scoped_release nogil;
+      HIP_CHECK(hipMemcpyAsync(d_agents_, ap, na * sizeof(u32),
+                               hipMemcpyHostToDevice, stream_));
+      hipLaunchKernelGGL(k_receive, dim3(na), dim3(256),
+                         (g_.recv_window + 2) * sizeof(u64), stream_,
+                         d_agents_, na, max_per_agent, priority ? 1 : 0,
+                         evict_base_, (const u64 *)nullptr, d_hdr_, d_status_,
+                         d_inbox_, d_wpos_, d_rpos_, d_carry_, d_carry_n_,
+                         d_bitmaps_, d_bitmap_epochs_, d_out_seqs_,
+                         d_out_counts_, d_by_status_, d_received_, g_);
+      u32 *d_offsets = reinterpret_cast<u32 *>(offsets_ptr);
+      hipLaunchKernelGGL(k_scan_counts, dim3(1), dim3(256), 4 * sizeof(u32),
+                         stream_, d_out_counts_, na, d_offsets);
+      // workgroups per agent: enough to give every wave one message,
+      // capped where the whole grid already covers the machine
+      const unsigned want = ((unsigned)max_per_agent + 3u) / 4u;
+      const unsigned fill =
+          (kDeliverBlocks + (unsigned)na - 1u) / (unsigned)na;
+      const unsigned split = std::max(1u, std::min(want, fill));
+      hipLaunchKernelGGL(k_deliver_device, dim3(na, split), dim3(256), 0,
+                         stream_,
+                         d_out_seqs_, d_out_counts_, d_offsets, na,
+                         max_per_agent, d_hdr_, d_payload_,
+                         reinterpret_cast<u8 *>(payload_ptr),
+                         reinterpret_cast<uint4 *>(headers_ptr),
+                         reinterpret_cast<long long *>(seqs_ptr),
+                         reinterpret_cast<int *>(lengths_ptr),
+                         reinterpret_cast<int *>(agent_row_ptr), stride, g_);
+      HIP_CHECK(hipMemcpyAsync(h_out_counts_, d_out_counts_, na * sizeof(u32),
+                               hipMemcpyDeviceToHost, stream_));
+      HIP_CHECK(hipStreamSynchronize(stream_));
+    }
+    std::memcpy(counts.mutable_data(), h_out_counts_, na * sizeof(u32));
+    last_recv_na_ = na;
+    last_recv_K_ = max_per_agent;
+    return counts;
+  }
+
+  // Mark `n` messages, named by an int64 device array, with `status`
+  // without the seqs ever visiting the host (see k_ack_device for the
+  // skip rules). Stream-ordered after the delivery; synchronizes.
+  void ack_device(uintptr_t seqs_ptr, long long n, u32 status) {
+    if (n < 0 || n > (long long)INT32_MAX)
+      throw std::invalid_argument("ack count out of range");
+    if (status >= (u32)N_STATUS)
+      throw std::invalid_argument("unknown status code");
+    if (n == 0)
+      return;
+    if (!seqs_ptr || seqs_ptr % 8)
+      throw std::invalid_argument("seqs buffer missing or misaligned");
+    py::gil_scoped_release nogil;
+    hipLaunchKernelGGL(k_ack_device, dim3((unsigned)((n + 255) / 256)),
+                       dim3(256), 0, stream_,
+                       reinterpret_cast<const long long *>(seqs_ptr), (int)n,
+                       status, evict_base_, count_, d_status_, d_by_status_,
+                       g_);
+    HIP_CHECK(hipStreamSynchronize(stream_));
+  }
+
   // ---- message store ----
 
   // Returns (hdr bytes [n*48], status[n], payload bytes [n*slot_bytes]).
@@ -1834,6 +2095,7 @@ public:
   u32 staging_batch() const { return staging_batch_; }
   u32 slot_bytes() const { return g_.slot_bytes; }
   u32 recv_window() const { return g_.recv_window; }
+  size_t out_pool() const { return out_pool_; }
 
 private:
   // Launch the enqueue kernel pair (+ fan-out) for n records at
@@ -1909,6 +2171,8 @@ private:
   hipEvent_t d2h_ev_[2] = {};
   int d2h_cur_ = 0;
   static constexpr int kSpree = 512;
+  // k_deliver_device grid target: 256 CUs x 8 resident workgroups
+  static constexpr unsigned kDeliverBlocks = 2048;
   int async_spree_ = 0;
   bool uploaded_[2] = {false, false};
   // captured steady-state tick (one exec per staging slot)
@@ -2370,6 +2634,14 @@ PYBIND11_MODULE(_swarmq, m) {
            py::arg("max_per_agent"), py::arg("priority"),
            py::arg("return_seqs") = true)
       .def("deliver_outbuf", &DeviceQueue::deliver_outbuf)
+      .def("receive_to_device", &DeviceQueue::receive_to_device,
+           py::arg("agents"), py::arg("max_per_agent"), py::arg("priority"),
+           py::arg("stride"), py::arg("payload_ptr"), py::arg("headers_ptr"),
+           py::arg("seqs_ptr"), py::arg("lengths_ptr"),
+           py::arg("agent_row_ptr"), py::arg("offsets_ptr"),
+           py::arg("capacity_rows"))
+      .def("ack_device", &DeviceQueue::ack_device, py::arg("seqs_ptr"),
+           py::arg("n"), py::arg("status"))
       .def("fetch", &DeviceQueue::fetch)
       .def("fetch_raw", &DeviceQueue::fetch_raw, py::arg("seqs"),
            py::arg("stride") = 0, py::arg("synchronize") = true)
@@ -2391,6 +2663,7 @@ PYBIND11_MODULE(_swarmq, m) {
       .def("staging_batch", &DeviceQueue::staging_batch)
       .def("slot_bytes", &DeviceQueue::slot_bytes)
       .def("recv_window", &DeviceQueue::recv_window)
+      .def("out_pool", &DeviceQueue::out_pool)
       .def("release", &DeviceQueue::release);
 
   py::class_<DoorbellQueue>(m, "DoorbellQueue")

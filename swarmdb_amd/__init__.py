@@ -12,6 +12,7 @@ persistence.
 
 from .core.config import QueueConfig
 from .core.message import Message, MessagePriority, MessageStatus, MessageType
+from .runtime.engine import DeviceDelivery
 from .runtime.facade import SwarmsDB
 
 __version__ = "0.2.0"
@@ -23,4 +24,5 @@ __all__ = [
     "MessageType",
     "MessagePriority",
     "MessageStatus",
+    "DeviceDelivery",
 ]

@@ -29,6 +29,7 @@ from .engine import (
     ST_DELIVERED,
     ST_FAILED,
     ST_PENDING,
+    ST_PROCESSED,
     ST_READ,
     VIS_BITMAP,
     VIS_GROUP,
@@ -294,6 +295,19 @@ class CpuEngine(Engine):
                     np.full(len(out), now_ms, dtype=np.uint64)
                 )
             return out.astype(np.uint64)
+
+    def receive_to_device(self, agent_idxs, max_per_agent,
+                          priority_order=False, max_payload=0, out=None):
+        # the base-class double, made one atomic step (dequeue + gather
+        # under the engine lock, as the GPU engine's single submission is)
+        with self._lock:
+            return super().receive_to_device(
+                agent_idxs, max_per_agent, priority_order, max_payload, out
+            )
+
+    def ack_device(self, seqs, n=None, status=ST_PROCESSED):
+        with self._lock:
+            super().ack_device(seqs, n, status)
 
     def peek_inbox(self, agent_idx: int) -> np.ndarray:
         with self._lock:

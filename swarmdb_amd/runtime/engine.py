@@ -25,7 +25,8 @@ on GPU). This replaces the reference's per-message produce path
 from __future__ import annotations
 
 import abc
-from typing import Dict, List, Optional, Tuple
+from dataclasses import dataclass
+from typing import Any, Dict, List, Optional, Tuple
 
 import numpy as np
 
@@ -93,6 +94,92 @@ REC_DTYPE = np.dtype(
         "itemsize": 48,
     }
 )
+
+
+def _to_numpy(x: Any) -> np.ndarray:
+    """Host copy of a numpy array or of a torch tensor (duck-typed: torch
+    is optional and must not be imported on the CPU path)."""
+    if hasattr(x, "detach"):
+        return x.detach().cpu().numpy()
+    return np.array(x, copy=True)
+
+
+@dataclass
+class DeviceDelivery:
+    """One poll tick delivered as packed, engine-resident arrays.
+
+    Message ``i`` of polled agent ``b`` sits in row ``r = offsets[b] + i``;
+    rows ``[0, total)`` are defined, the buffers may be longer (capacity
+    ``len(counts) * max_per_agent``). On the GPU engine every array but
+    ``counts`` is a ``torch.Tensor`` in HBM on the queue's device — a
+    model on the same GPU reads its inbox without a PCIe crossing; on the
+    CPU engine they are numpy arrays with the same dtypes and layout.
+    ``counts`` is the one thing the GPU engine brings to the host
+    (``4 * len(counts)`` bytes), so it is a host int64 array on both.
+
+    - ``counts``     int64 [na]      messages delivered per polled agent
+    - ``offsets``    int32 [na + 1]  exclusive prefix sum, ``[na] == total``
+    - ``seqs``       int64 [rows]    sequence numbers
+    - ``lengths``    int32 [rows]    ``min(payload_len, stride)``
+    - ``agent_row``  int32 [rows]    position ``b`` in the polled list
+    - ``headers``    uint8 [rows,48] REC_DTYPE records, ``payload_off``
+      rebased to ``r * stride`` (into ``payload``, flattened)
+    - ``payload``    uint8 [rows, stride], zero from ``lengths[r]`` on
+    """
+
+    counts: Any
+    offsets: Any
+    seqs: Any
+    lengths: Any
+    agent_row: Any
+    headers: Any
+    payload: Any
+    stride: int
+    total: int
+
+    def to_host(self) -> "DeviceDelivery":
+        """Copy with numpy arrays, trimmed to ``total`` rows; ``headers``
+        comes back as a REC_DTYPE array."""
+        t = self.total
+        headers = np.ascontiguousarray(_to_numpy(self.headers[:t]))
+        return DeviceDelivery(
+            counts=_to_numpy(self.counts),
+            offsets=_to_numpy(self.offsets),
+            seqs=_to_numpy(self.seqs[:t]),
+            lengths=_to_numpy(self.lengths[:t]),
+            agent_row=_to_numpy(self.agent_row[:t]),
+            headers=headers.view(REC_DTYPE).reshape(-1),
+            payload=_to_numpy(self.payload[:t]),
+            stride=self.stride,
+            total=t,
+        )
+
+
+def delivery_stride(max_payload: int, slot_bytes: int) -> int:
+    """Row stride of a device-resident delivery: ``max_payload`` rounded up
+    to 16 B when it tightens the row below ``slot_bytes``."""
+    if 0 < max_payload < slot_bytes:
+        return (int(max_payload) + 15) // 16 * 16
+    return int(slot_bytes)
+
+
+def check_delivery_out(
+    out: DeviceDelivery, n_agents: int, rows: int, stride: int
+) -> None:
+    """Refuse (ValueError) a reused delivery whose buffers cannot hold a
+    poll of ``n_agents`` x ``rows / n_agents``. Runs BEFORE any dequeue."""
+    if out.stride != stride:
+        raise ValueError(
+            f"out has stride {out.stride}, this call needs {stride}"
+        )
+    if len(out.offsets) < n_agents + 1:
+        raise ValueError("out.offsets is too small for the polled agents")
+    for name in ("seqs", "lengths", "agent_row", "headers", "payload"):
+        if len(getattr(out, name)) < rows:
+            raise ValueError(
+                f"out.{name} holds {len(getattr(out, name))} rows, "
+                f"this call needs {rows}"
+            )
 
 
 class Engine(abc.ABC):
@@ -168,6 +255,96 @@ class Engine(abc.ABC):
             np.concatenate(chunks) if chunks else np.empty(0, dtype=np.uint64)
         )
         return counts, seqs
+
+    def receive_to_device(
+        self,
+        agent_idxs: np.ndarray,
+        max_per_agent: int,
+        priority_order: bool = False,
+        max_payload: int = 0,
+        out: Optional[DeviceDelivery] = None,
+    ) -> DeviceDelivery:
+        """Drain many agents into packed engine-resident arrays (see
+        :class:`DeviceDelivery`). ``max_payload`` (if known) tightens the
+        row stride below slot_bytes; longer payloads are truncated in the
+        delivery (``lengths`` says to what) while the header keeps the
+        true ``payload_len``. ``out`` reuses the buffers of an earlier
+        delivery; one that is too small raises ValueError before anything
+        is dequeued. Default: the CPU double on :meth:`receive_many` +
+        :meth:`fetch_raw_chunks`, same layout and zero tails as the GPU
+        engine's single stream-ordered submission."""
+        agent_idxs = np.ascontiguousarray(agent_idxs, dtype=np.uint32)
+        na, K = len(agent_idxs), int(max_per_agent)
+        if K < 0:
+            raise ValueError("max_per_agent must be >= 0")
+        stride = delivery_stride(
+            max_payload, self.cfg.slot_bytes  # type: ignore[attr-defined]
+        )
+        rows = na * K
+        if out is not None:
+            check_delivery_out(out, na, rows, stride)
+            offsets = out.offsets[: na + 1]
+            seqs_o, lengths, agent_row = out.seqs, out.lengths, out.agent_row
+            headers, payload = out.headers, out.payload
+        else:
+            offsets = np.zeros(na + 1, dtype=np.int32)
+            seqs_o = np.zeros(rows, dtype=np.int64)
+            lengths = np.zeros(rows, dtype=np.int32)
+            agent_row = np.zeros(rows, dtype=np.int32)
+            headers = np.zeros((rows, REC_DTYPE.itemsize), dtype=np.uint8)
+            payload = np.zeros((rows, stride), dtype=np.uint8)
+        counts, seqs = self.receive_many(agent_idxs, K, priority_order)
+        counts = np.asarray(counts, dtype=np.int64)
+        total = int(counts.sum())
+        offsets[0] = 0
+        offsets[1:] = np.cumsum(counts)
+        if total:
+            hdrs, flat, fstride = self.fetch_raw_chunks(seqs)
+            flat = flat.reshape(total, fstride)
+            lens = np.minimum(hdrs["payload_len"], stride).astype(np.int32)
+            w = min(stride, fstride)
+            payload[:total, :w] = flat[:, :w]
+            payload[:total, w:] = 0
+            dead = np.arange(stride, dtype=np.int32)[None, :] >= lens[:, None]
+            payload[:total][dead] = 0
+            recs = np.zeros(total, dtype=REC_DTYPE)
+            for name in REC_DTYPE.names:
+                recs[name] = hdrs[name]
+            recs["payload_off"] = np.arange(total, dtype=np.uint64) * np.uint64(
+                stride
+            )
+            headers[:total] = recs.view(np.uint8).reshape(
+                total, REC_DTYPE.itemsize
+            )
+            seqs_o[:total] = seqs.astype(np.int64)
+            lengths[:total] = lens
+            agent_row[:total] = np.repeat(
+                np.arange(na, dtype=np.int32), counts
+            )
+        return DeviceDelivery(
+            counts=counts, offsets=offsets, seqs=seqs_o, lengths=lengths,
+            agent_row=agent_row, headers=headers, payload=payload,
+            stride=stride, total=total,
+        )
+
+    def ack_device(
+        self, seqs: Any, n: Optional[int] = None, status: int = ST_PROCESSED
+    ) -> None:
+        """Mark the first ``n`` (default: all) of ``seqs`` — the int64
+        ``seqs`` array of a :class:`DeviceDelivery`, or a selection of it —
+        with ``status``. A seq below the retention horizon is skipped (its
+        slot holds a newer message), as is one never assigned; a deleted
+        message stays deleted. Default: a host loop (the CPU double); the
+        GPU engine reads the seqs straight from HBM in one kernel."""
+        arr = np.asarray(_to_numpy(seqs), dtype=np.int64).reshape(-1)
+        n = len(arr) if n is None else int(n)
+        if not 0 <= n <= len(arr):
+            raise ValueError("n must be within 0..len(seqs)")
+        lo, hi = self.evict_base(), self.total_messages()
+        for s in arr[:n].tolist():
+            if s < lo or s >= hi or self.get_status(s) == ST_DELETED:
+                continue
+            self.set_status(s, int(status))
 
     @abc.abstractmethod
     def peek_inbox(self, agent_idx: int) -> np.ndarray:

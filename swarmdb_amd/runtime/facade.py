@@ -61,12 +61,18 @@ from .engine import (
     VIS_ALL,
     VIS_BITMAP,
     VIS_GROUP,
+    DeviceDelivery,
     Engine,
 )
 
 logger = logging.getLogger("swarmdb_amd")
 
 _STATUS_CODES = {n: i for i, n in enumerate(STATUS_NAMES)}
+
+# the row layout _reconstruct reads: what Engine.fetch returns
+_DELIVERY_ROW_DTYPE = np.dtype(
+    REC_DTYPE.descr + [("status", np.uint8), ("seq", np.uint64)]
+)
 
 
 def _status_code(status: Union[MessageStatus, str]) -> int:
@@ -609,6 +615,85 @@ class SwarmsDB:
         with self._lock:
             self.register_agent(agent_id)
             return self._agent_idx[agent_id]
+
+    # ------------------------------------------------------------------
+    # device-resident delivery (new — GPU-local consumers read inboxes
+    # from HBM; no REST route: a device tensor has no HTTP representation)
+    # ------------------------------------------------------------------
+
+    def receive_device(
+        self,
+        agent_ids: List[str],
+        max_messages: int = 100,
+        priority_order: bool = False,
+        max_payload: int = 0,
+    ) -> DeviceDelivery:
+        """Poll many agents and leave the deliveries where the engine
+        keeps them: on the GPU engine the result's arrays are torch
+        tensors in HBM (see :class:`DeviceDelivery`), on the CPU engine
+        numpy arrays of the same layout. Unknown agents are
+        auto-registered, as in :meth:`receive_messages`; row ``b`` of
+        ``counts``/``offsets`` belongs to ``agent_ids[b]``. Messages are
+        marked READ; hand the delivery to :meth:`ack_device` once
+        consumed."""
+        with self._lock:
+            for a in agent_ids:
+                self.register_agent(a)
+            idxs = np.array(
+                [self._agent_idx[a] for a in agent_ids], dtype=np.uint32
+            )
+        with tracer.span("receive_device", n=len(idxs)):
+            return self.engine.receive_to_device(
+                idxs, max_messages, priority_order, max_payload
+            )
+
+    def ack_device(
+        self,
+        delivery_or_seqs,
+        status: Union[MessageStatus, str] = MessageStatus.PROCESSED,
+    ) -> None:
+        """Mark every message of a :class:`DeviceDelivery` (or of a seq
+        array / device tensor, e.g. a selection of ``delivery.seqs``)
+        with ``status`` — on the GPU engine without the sequence numbers
+        leaving the device. Evicted and deleted messages are skipped."""
+        code = _status_code(status)
+        with tracer.span("ack_device"):
+            if isinstance(delivery_or_seqs, DeviceDelivery):
+                self.engine.ack_device(
+                    delivery_or_seqs.seqs, delivery_or_seqs.total, code
+                )
+            else:
+                self.engine.ack_device(delivery_or_seqs, None, code)
+
+    def messages_from_delivery(
+        self, delivery: DeviceDelivery
+    ) -> List[List[Message]]:
+        """Decode a delivery into Message objects, one list per polled
+        agent — the debugging / parity bridge to the compat path (a host
+        copy plus per-message Python work; not a hot path). Oversized
+        messages resolve from the host-side overflow store, ids and
+        extras decode exactly as in :meth:`receive_messages`."""
+        h = delivery.to_host()
+        if (h.lengths < h.headers["payload_len"]).any():
+            raise ValueError(
+                "delivery was truncated by max_payload; it cannot be decoded"
+            )
+        rows = np.zeros(h.total, dtype=_DELIVERY_ROW_DTYPE)
+        for name in REC_DTYPE.names:
+            rows[name] = h.headers[name]
+        rows["seq"] = h.seqs.astype(np.uint64)
+        if h.total:
+            rows["status"] = self.engine.statuses(rows["seq"])
+        out: List[List[Message]] = []
+        for b in range(len(h.counts)):
+            lo, hi = int(h.offsets[b]), int(h.offsets[b + 1])
+            out.append([
+                self._reconstruct(
+                    rows[r], h.payload[r, : int(h.lengths[r])].tobytes()
+                )
+                for r in range(lo, hi)
+            ])
+        return out
 
     # ------------------------------------------------------------------
     # receive / read path (reference swarmdb/ main.py:521-781, 1026-1047)

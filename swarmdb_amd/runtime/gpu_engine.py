@@ -11,6 +11,7 @@ no silent eager fallback (use CpuEngine explicitly for CPU runs).
 
 from __future__ import annotations
 
+import sys
 import threading
 import time
 from typing import Dict, List, Optional, Tuple
@@ -21,7 +22,11 @@ from ..core.config import QueueConfig
 from .engine import (
     REC_DTYPE,
     ST_DELETED,
+    ST_PROCESSED,
+    DeviceDelivery,
     Engine,
+    check_delivery_out,
+    delivery_stride,
 )
 
 _FETCH_DTYPE = np.dtype(REC_DTYPE.descr + [("status", np.uint8), ("seq", np.uint64)])
@@ -43,6 +48,16 @@ class GpuEngine(Engine):
     def __init__(self, config: Optional[QueueConfig] = None):
         self.cfg = config or QueueConfig()
         c = self.cfg
+        # torch carries a HIP runtime of its own, and it only finds the
+        # GPU if it initialises BEFORE this extension's runtime does
+        # (measured: the other order ends in "No HIP GPUs are available").
+        # A process that already imported torch — any consumer of
+        # receive_to_device has — gets that order here; torch stays
+        # optional and is never imported on behalf of a caller without it
+        torch = sys.modules.get("torch")
+        if torch is not None and torch.cuda.is_available():
+            torch.cuda.init()
+        self._torch_dev = None  # set by _torch_device on first use
         ext = _load_ext()
         if ext.device_count() == 0:  # pragma: no cover
             raise RuntimeError(
@@ -206,6 +221,10 @@ class GpuEngine(Engine):
         mat = flat.reshape(len(agent_idxs), max_per_agent)
         mask = np.arange(max_per_agent)[None, :] < counts[:, None]
         seqs = mat[mask]
+        self._note_receive(agent_idxs, counts)
+        return counts, seqs
+
+    def _note_receive(self, agent_idxs: np.ndarray, counts: np.ndarray) -> None:
         # O(1)-per-tick receive-rate bookkeeping (processing_rate probe).
         # Prune by AGE, not entry count: a fixed-count prune truncated the
         # 60 s probe window under sustained polling (>~17 ticks/s). The
@@ -220,7 +239,112 @@ class GpuEngine(Engine):
                 if t >= cutoff:
                     break
             del self._recv_events[:i]
-        return counts, seqs
+
+    def _torch_device(self):
+        """(torch, device) of the queue's GPU for the device-resident
+        delivery path; a clear error when torch cannot see the GPU."""
+        import torch
+
+        if self._torch_dev is None:
+            if not torch.cuda.is_available():
+                raise RuntimeError(
+                    "torch sees no HIP device: import torch before "
+                    "constructing GpuEngine, so that torch's HIP runtime "
+                    "initialises first"
+                )
+            self._torch_dev = torch.device("cuda", self.cfg.device_index)
+        return torch, self._torch_dev
+
+    def receive_to_device(
+        self,
+        agent_idxs: np.ndarray,
+        max_per_agent: int,
+        priority_order: bool = False,
+        max_payload: int = 0,
+        out: Optional[DeviceDelivery] = None,
+    ) -> DeviceDelivery:
+        """Dequeue + device prefix scan + packed delivery into torch
+        tensors on the queue's GPU, one stream-ordered submission; only
+        the per-agent counts cross PCIe. The engine's stream is not one
+        of torch's, so the caller's current torch stream is drained
+        first (pending consumers of reused or recycled buffers) and the
+        submission is synchronized before return: the tensors are safe on
+        any torch stream afterwards."""
+        torch, dev = self._torch_device()
+        agent_idxs = np.ascontiguousarray(agent_idxs, dtype=np.uint32)
+        na, K = len(agent_idxs), int(max_per_agent)
+        if K < 0:
+            raise ValueError("max_per_agent must be >= 0")
+        stride = delivery_stride(max_payload, self._slot_bytes)
+        rows = na * K
+        # every refusal happens here or in the binding's own checks —
+        # before the dequeue kernel moves a cursor
+        if na > self.cfg.max_agents:
+            raise ValueError("more polled agents than max_agents")
+        if rows > self.q.out_pool():
+            raise ValueError("receive batch exceeds output pool")
+        if out is not None:
+            check_delivery_out(out, na, rows, stride)
+            for name in ("offsets", "seqs", "lengths", "agent_row",
+                         "headers", "payload"):
+                t = getattr(out, name)
+                if not (isinstance(t, torch.Tensor) and t.device == dev
+                        and t.is_contiguous()):
+                    raise ValueError(
+                        f"out.{name} must be a contiguous tensor on {dev}"
+                    )
+            offsets = out.offsets[: na + 1]
+            seqs, lengths, agent_row = out.seqs, out.lengths, out.agent_row
+            headers, payload = out.headers, out.payload
+        else:
+            offsets = torch.zeros(na + 1, dtype=torch.int32, device=dev)
+            seqs = torch.empty(rows, dtype=torch.int64, device=dev)
+            lengths = torch.empty(rows, dtype=torch.int32, device=dev)
+            agent_row = torch.empty(rows, dtype=torch.int32, device=dev)
+            headers = torch.empty(
+                (rows, REC_DTYPE.itemsize), dtype=torch.uint8, device=dev
+            )
+            payload = torch.empty((rows, stride), dtype=torch.uint8, device=dev)
+        torch.cuda.current_stream(dev).synchronize()
+        with self._lock:
+            counts = self.q.receive_to_device(
+                agent_idxs, K, bool(priority_order), stride,
+                payload.data_ptr(), headers.data_ptr(), seqs.data_ptr(),
+                lengths.data_ptr(), agent_row.data_ptr(), offsets.data_ptr(),
+                int(payload.shape[0]),
+            )
+        counts = counts.astype(np.int64)
+        total = int(counts.sum())
+        if total:
+            self._note_receive(agent_idxs, counts)
+        return DeviceDelivery(
+            counts=counts, offsets=offsets, seqs=seqs, lengths=lengths,
+            agent_row=agent_row, headers=headers, payload=payload,
+            stride=stride, total=total,
+        )
+
+    def ack_device(
+        self, seqs, n: Optional[int] = None, status: int = ST_PROCESSED
+    ) -> None:
+        """One kernel over an int64 device tensor of seqs (contiguous, on
+        the queue's GPU — e.g. ``delivery.seqs`` or a selection of it);
+        anything else is converted to one first. Skip rules as in
+        :meth:`Engine.ack_device`."""
+        torch, dev = self._torch_device()
+        if not isinstance(seqs, torch.Tensor):
+            seqs = torch.from_numpy(
+                np.ascontiguousarray(seqs).astype(np.int64).reshape(-1)
+            )
+        t = seqs.to(device=dev, dtype=torch.int64).contiguous().reshape(-1)
+        n = t.numel() if n is None else int(n)
+        if not 0 <= n <= t.numel():
+            raise ValueError("n must be within 0..len(seqs)")
+        if n == 0:
+            return
+        # the seqs may come from kernels still running on torch's stream
+        torch.cuda.current_stream(dev).synchronize()
+        with self._lock:
+            self.q.ack_device(t.data_ptr(), n, int(status))
 
     def peek_inbox(self, agent_idx: int) -> np.ndarray:
         _, entries = self.q.inbox_window(int(agent_idx))
