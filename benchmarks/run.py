@@ -13,9 +13,13 @@
                    spill
  10 p2p-device     config 2's traffic, delivered into HBM tensors and
                    acked from the device (no payload or seq D2H)
+ 11 echo-device    config 10's traffic as an echo loop: every delivered
+                   message is answered from a device tensor
+                   (reply_to_device); --host-return answers through the
+                   host instead (D2H, host records, enqueue_batch)
 
 Usage:
-  python -m benchmarks.run --config {1,2,3,5,10} [--seconds S]
+  python -m benchmarks.run --config {1,2,3,5,10,11} [--seconds S]
   python -m torch.distributed.run --nproc-per-node N benchmarks/run.py --config 4
 
 Each config prints one JSON line:
@@ -211,6 +215,88 @@ def config10_device_delivery(seconds: float) -> None:
     _emit(10, "p2p-gpu-1kb-device-resident", n, elapsed,
           float(np.median(lat) * 1000),
           {"delivery": "device", "stride": d.stride})
+
+
+def config11_device_echo(seconds: float, host_return: bool = False) -> None:
+    """Config 10's traffic (2 agents, 4096 x 1 KB per tick) turned into an
+    echo loop: enqueue_batch 0 -> 1, receive_to_device for agent 1, one
+    torch op on the delivered payload tensor writing a preallocated
+    reply tensor, the reply 1 -> 0, ack_device, and a device poll of
+    agent 0 so that no inbox fills. The reply goes out with
+    reply_to_device (records built on the device, payload rows read in
+    place; one word comes back), or with ``host_return`` the only way
+    there was before it: reply and headers to the host, records built
+    there, enqueue_batch (4 MB D2H + 4 MB H2D per tick)."""
+    import torch  # before GpuEngine: torch's HIP runtime first
+
+    from swarmdb_amd.runtime.engine import FLAG_DERIVED_ID, TYPE_CODES
+    from swarmdb_amd.runtime.gpu_engine import GpuEngine
+
+    cfg = QueueConfig(use_gpu=True, auto_save=False, max_agents=64,
+                      num_slots=1 << 20, staging_batch=16384)
+    eng = GpuEngine(cfg)
+    eng.register_agent(0)
+    eng.register_agent(1)
+    rng = np.random.default_rng(0)
+    batch = 4096  # one dequeue window, as in config 2
+    recs, payload = _make_batch(rng, batch, np.array([0]), np.array([1]), 1024)
+    consumer = np.array([1], dtype=np.uint32)
+    producer = np.array([0], dtype=np.uint32)
+    code = TYPE_CODES["function_result"]
+    state = {"d": None, "back": None, "reply": None}
+
+    def tick():
+        eng.enqueue_batch(recs, payload)
+        d = state["d"] = eng.receive_to_device(
+            consumer, batch, max_payload=1024, out=state["d"])
+        if state["reply"] is None:
+            state["reply"] = torch.empty_like(d.payload)
+        reply = state["reply"]
+        torch.bitwise_xor(d.payload, 0x20, out=reply)  # the "model"
+        if host_return:
+            t = d.total
+            hdr = d.headers[:t].cpu().numpy().view(REC_DTYPE).reshape(-1)
+            lens = d.lengths[:t].cpu().numpy()
+            out = np.zeros(t, dtype=REC_DTYPE)
+            out["sender"] = consumer[0]
+            out["receiver"] = hdr["sender"]
+            out["type"] = code
+            out["priority"] = hdr["priority"]
+            out["vis_mode"] = VIS_ALL
+            out["flags"] = FLAG_DERIVED_ID
+            out["timestamp"] = time.time()
+            out["bitmap"] = NO_BITMAP
+            out["payload_len"] = out["content_len"] = lens
+            out["payload_off"] = np.arange(t, dtype=np.uint64) * d.stride
+            sent = eng.enqueue_batch(out, reply[:t].cpu().numpy().reshape(-1))
+        else:
+            sent = eng.reply_to_device(d, consumer, reply, d.lengths, code)
+        eng.ack_device(d.seqs, n=d.total)
+        back = state["back"] = eng.receive_to_device(
+            producer, batch, max_payload=1024, out=state["back"])
+        assert d.total == len(sent) == back.total == batch, \
+            "echo tick failed to drain"
+        return d.total
+
+    lat = []
+    n = 0
+    for _ in range(3):  # warmup
+        tick()
+    t0 = time.perf_counter()
+    while time.perf_counter() - t0 < seconds:
+        s = time.perf_counter()
+        n += tick()
+        lat.append(time.perf_counter() - s)
+    elapsed = time.perf_counter() - t0
+    # spot-check the last tick's echoes (outside the timed region)
+    h = state["back"].to_host()
+    src = np.frombuffer(payload, dtype=np.uint8)[: batch * 1024] ^ np.uint8(0x20)
+    assert np.array_equal(h.payload.reshape(-1), src), "echo mismatch"
+    assert (h.headers["sender"] == 1).all() and (h.headers["type"] == code).all()
+    eng.close()
+    _emit(11, "p2p-gpu-1kb-echo", n, elapsed, float(np.median(lat) * 1000),
+          {"return": "host" if host_return else "device",
+           "stride": state["d"].stride})
 
 
 def config3_group_fanout(seconds: float) -> None:
@@ -619,8 +705,10 @@ def config5_loadbalancer(seconds: float) -> None:
 def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", type=int, required=True,
-                    choices=[1, 2, 3, 4, 5, 6, 7, 8, 9, 10])
+                    choices=[1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11])
     ap.add_argument("--seconds", type=float, default=5.0)
+    ap.add_argument("--host-return", action="store_true",
+                    help="config 11: send the replies through the host")
     args = ap.parse_args()
     if args.config == 1:
         config1_cpu_loopback(args.seconds)
@@ -653,6 +741,8 @@ def main() -> int:
         config9_distributed_service(args.seconds)
     elif args.config == 10:
         config10_device_delivery(args.seconds)
+    elif args.config == 11:
+        config11_device_echo(args.seconds, args.host_return)
     return 0
 
 

@@ -916,6 +916,132 @@ __global__ void k_ack_device(const long long *__restrict__ seqs, int n,
   }
 }
 
+// ---- device-resident send ----
+//
+// The records of a device-side producer live in a tensor the host never
+// sees, so nothing in them may steer a read. Both kernels below write
+// SANITISED records into the engine's own buffer, and the unchanged
+// enqueue kernels run on that copy: payload_off is always
+// (engine-derived row) * stride, and a length above the stride — the
+// 16-B round-up of any smaller one stays inside the row, the stride
+// being a multiple of 16 — is replaced by OVERSIZE, which k_enqueue_meta
+// parks FAILED and k_enqueue_payload never copies.
+constexpr u32 OVERSIZE = 0xFFFFFFFFu;
+
+__device__ inline void store_rec(Rec *dst, const Rec &r) {
+  uint4 v[3];
+  __builtin_memcpy(v, &r, sizeof(Rec));
+  uint4 *o = reinterpret_cast<uint4 *>(dst);
+  o[0] = v[0];
+  o[1] = v[1];
+  o[2] = v[2];
+}
+
+// Sanitise caller records: one thread per record, three 16-B loads from
+// the caller's tensor. Record i owns payload row i, whatever its own
+// payload_off says. The visibility-bitmap HANDLE is split here into
+// (pool slot, epoch), as GpuEngine.split_bitmap_handles does on the
+// host path; an incoming bitmap_epoch is never trusted.
+__global__ void __launch_bounds__(256)
+    k_stage_device(const uint4 *__restrict__ src, int n, u32 stride,
+                   u32 num_bitmaps, Rec *__restrict__ dst) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n)
+    return;
+  uint4 v[3];
+  v[0] = src[(u64)i * 3];
+  v[1] = src[(u64)i * 3 + 1];
+  v[2] = src[(u64)i * 3 + 2];
+  Rec r;
+  __builtin_memcpy(&r, v, sizeof(Rec));
+  r.payload_off = (u64)i * stride;
+  if (r.payload_len > stride)
+    r.payload_len = OVERSIZE;
+  if (r.vis_mode != VIS_ALL && r.bitmap != NO_BITMAP) {
+    r.bitmap_epoch = r.bitmap;
+    r.bitmap = r.bitmap % num_bitmaps;
+  } else {
+    r.bitmap_epoch = 0;
+  }
+  store_rec(dst + i, r);
+}
+
+// Replies to a device-resident delivery. Row r is answered iff
+// lengths[r] >= 0, and the answers are numbered in row order, so the
+// kept rows need a stable compaction across workgroups. Two passes over
+// the 4-byte lengths, one thread per row in 256-thread workgroups:
+// k_reply_count leaves the kept rows of each workgroup, k_scan_counts
+// turns those into workgroup offsets (and the total m, the one word the
+// host reads back), and k_build_replies ranks each kept row inside its
+// workgroup — a ballot + popcount per wave, the four wave totals through
+// LDS — and writes its record at offset + rank.
+__global__ void __launch_bounds__(256)
+    k_reply_count(const int *__restrict__ lengths, int total,
+                  u32 *__restrict__ block_counts) {
+  __shared__ u32 wave_tot[4];
+  const int r = blockIdx.x * 256 + (int)threadIdx.x;
+  const bool keep = r < total && lengths[r] >= 0;
+  const ull mask = __ballot(keep);
+  if ((threadIdx.x & 63) == 0)
+    wave_tot[threadIdx.x >> 6] = (u32)__popcll(mask);
+  __syncthreads();
+  if (threadIdx.x == 0)
+    block_counts[blockIdx.x] =
+        wave_tot[0] + wave_tot[1] + wave_tot[2] + wave_tot[3];
+}
+
+// The reply to delivered row r: sender = the polled agent of the row
+// (agents[agent_row[r]] — not the delivered receiver, which may be
+// BROADCAST), receiver = the delivered sender, payload = row r of the
+// caller's reply tensor. headers and agent_row are tensors the consumer
+// could have written to, so an agent_row outside the polled list gives
+// sender BROADCAST (out of range: the error lane) and is never used as
+// an index; every other field is copied as a value, not followed.
+__global__ void __launch_bounds__(256)
+    k_build_replies(const uint4 *__restrict__ headers,
+                    const int *__restrict__ agent_row,
+                    const int *__restrict__ lengths, int total,
+                    const u32 *__restrict__ agents, int n_agents,
+                    const u32 *__restrict__ block_offsets, u32 rstride,
+                    u32 type_code, int priority, u32 flags, double timestamp,
+                    Rec *__restrict__ dst) {
+  __shared__ u32 wave_tot[4];
+  const u32 lane = threadIdx.x & 63;
+  const u32 wave = threadIdx.x >> 6;
+  const int r = blockIdx.x * 256 + (int)threadIdx.x;
+  const int len = r < total ? lengths[r] : -1;
+  const bool keep = len >= 0;
+  const ull mask = __ballot(keep);
+  if (lane == 0)
+    wave_tot[wave] = (u32)__popcll(mask);
+  __syncthreads();
+  if (!keep)
+    return;
+  u32 before = 0;
+  for (u32 w = 0; w < wave; ++w)
+    before += wave_tot[w];
+  const u32 rank = (u32)__popcll(mask & ((1ull << lane) - 1ull));
+  const u32 j = block_offsets[blockIdx.x] + before + rank;
+
+  const uint4 h0 = headers[(u64)r * 3]; // sender .x, type/priority/.. .z
+  const int b = agent_row[r];
+  Rec o;
+  o.sender = (b >= 0 && b < n_agents) ? agents[b] : BROADCAST;
+  o.receiver = h0.x;
+  o.type = (u8)type_code;
+  o.priority = priority >= 0 ? (u8)priority : (u8)((h0.z >> 8) & 0xFFu);
+  o.vis_mode = VIS_ALL;
+  o.flags = (u8)flags;
+  o.token_count = 0;
+  o.timestamp = timestamp;
+  o.payload_off = (u64)r * rstride;
+  o.payload_len = (u32)len > rstride ? OVERSIZE : (u32)len;
+  o.bitmap = NO_BITMAP;
+  o.content_len = (u32)len;
+  o.bitmap_epoch = 0;
+  store_rec(dst + j, o);
+}
+
 // Status mutation with counter upkeep (mark processed / admin status
 // updates / delete tombstones).
 __global__ void k_set_status(u64 seq, u32 new_status, u32 *__restrict__ status,
@@ -1104,6 +1230,16 @@ public:
     HIP_CHECK(hipMemset(d_sent_, 0, (size_t)max_agents * sizeof(ull)));
     HIP_CHECK(hipMemset(d_received_, 0, (size_t)max_agents * sizeof(ull)));
     HIP_CHECK(hipMemset(d_backend_loads_, 0, (size_t)num_backends * sizeof(ull)));
+
+    // device-resident send: sanitised records, and the per-workgroup
+    // reply counts / offsets of the compaction (256 rows per workgroup).
+    // Allocated last, so that every buffer above sits where it did
+    // before these existed (profiles/device_send.md)
+    const size_t reply_blocks = ((size_t)staging_batch + 255) / 256;
+    HIP_CHECK(hipMalloc(&d_dev_recs_, (size_t)staging_batch * sizeof(Rec)));
+    HIP_CHECK(hipMalloc(&d_reply_blk_, reply_blocks * sizeof(u32)));
+    HIP_CHECK(hipMalloc(&d_reply_off_, (reply_blocks + 1) * sizeof(u32)));
+    HIP_CHECK(hipHostMalloc(&h_reply_m_, sizeof(u32)));
   }
 
   ~DeviceQueue() { release(); }
@@ -1126,13 +1262,14 @@ public:
                              d_out_seqs_, d_out_counts_, d_stage_recs_[0],
                              d_stage_recs_[1], d_stage_pay_[0],
                              d_stage_pay_[1], d_seqs_in_, d_fetch_hdr_,
-                             d_fetch_status_, d_fetch_pay_})
+                             d_fetch_status_, d_fetch_pay_, d_dev_recs_,
+                             d_reply_blk_, d_reply_off_})
       (void)hipFree(p);
     for (void *p : std::vector<void *>{h_recs_[0], h_recs_[1], h_pay_[0],
                                        h_pay_[1], h_out_seqs_,
                                        h_out_counts_, h_fetch_hdr_,
                                        h_fetch_status_, h_fetch_pay_,
-                                       h_choices_})
+                                       h_choices_, h_reply_m_})
       (void)hipHostFree(p);
     (void)hipEventDestroy(stage_ev_[0]);
     (void)hipEventDestroy(stage_ev_[1]);
@@ -1489,6 +1626,109 @@ public:
     if (count_ > g_.num_slots)
       evict_base_ = count_ - g_.num_slots;
     return base;
+  }
+
+  // Device-resident send: n REC_DTYPE records in a caller tensor
+  // (`headers_ptr`, 48 B each) whose record i owns row i of the
+  // [n, stride] payload tensor at `payload_ptr`. k_stage_device copies
+  // the records into the engine's own buffer with every value a read
+  // depends on forced or bounded (see the kernel), then the ordinary
+  // enqueue kernels run on that copy. At most staging_batch records per
+  // call (d_bcast_ and the record buffer hold that many); the caller
+  // chunks. Every check runs before anything is launched. Synchronizes,
+  // so the caller may overwrite its tensors afterwards.
+  u64 enqueue_from_device(uintptr_t headers_ptr, uintptr_t payload_ptr, int n,
+                          u32 stride) {
+    if (n < 0 || (u32)n > staging_batch_)
+      throw std::invalid_argument("batch exceeds staging_batch");
+    check_row_stride(stride);
+    if (n == 0)
+      return count_;
+    if (!headers_ptr || !payload_ptr)
+      throw std::invalid_argument("send buffer pointer is null");
+    if (headers_ptr % 16 || payload_ptr % 16)
+      throw std::invalid_argument("send buffer is misaligned");
+    const u64 base = count_;
+    {
+      py::gil_scoped_release nogil;
+      hipLaunchKernelGGL(k_stage_device, dim3((n + 255) / 256), dim3(256), 0,
+                         stream_, reinterpret_cast<const uint4 *>(headers_ptr),
+                         n, stride, g_.num_bitmaps, d_dev_recs_);
+      HIP_CHECK(hipMemsetAsync(d_bcast_count_, 0, sizeof(u32), stream_));
+      launch_enqueue(d_dev_recs_, reinterpret_cast<const u8 *>(payload_ptr), n,
+                     base);
+      HIP_CHECK(hipStreamSynchronize(stream_));
+    }
+    count_ = base + (u64)n;
+    if (count_ > g_.num_slots)
+      evict_base_ = count_ - g_.num_slots;
+    return base;
+  }
+
+  // Reply to the first `total` rows of a device-resident delivery from
+  // device tensors: row r is answered iff lengths[r] >= 0, with row r of
+  // the [>= total, rstride] reply tensor as payload (k_build_replies has
+  // the field rules). Replies are numbered in row order; returns
+  // (base seq, m). Only the polled agents (na words) go to the device
+  // and only m (4 B) comes back. `total` is bounded by staging_batch,
+  // like any batch; the caller splits a larger delivery by rows.
+  // `priority` < 0 inherits the delivered message's. Every check runs
+  // before anything is launched; synchronizes.
+  py::tuple reply_from_device(uintptr_t headers_ptr, uintptr_t agent_row_ptr,
+                              uintptr_t lengths_ptr, uintptr_t payload_ptr,
+                              int total, u32 rstride, py::array_t<u32> agents,
+                              u32 type_code, int priority, u32 flags,
+                              double timestamp) {
+    const int na = (int)agents.size();
+    if (total < 0 || (u32)total > staging_batch_)
+      throw std::invalid_argument("batch exceeds staging_batch");
+    check_row_stride(rstride);
+    if ((u32)na > g_.max_agents)
+      throw std::invalid_argument("more polled agents than max_agents");
+    if (priority > 255 || type_code > 255u || flags > 255u)
+      throw std::invalid_argument("type, priority and flags are one byte");
+    if (total == 0)
+      return py::make_tuple(count_, 0u);
+    if (!headers_ptr || !agent_row_ptr || !lengths_ptr || !payload_ptr)
+      throw std::invalid_argument("reply buffer pointer is null");
+    if (headers_ptr % 16 || payload_ptr % 16 || agent_row_ptr % 4 ||
+        lengths_ptr % 4)
+      throw std::invalid_argument("reply buffer is misaligned");
+    const u64 base = count_;
+    const int nblk = (total + 255) / 256;
+    u32 m = 0;
+    {
+      py::gil_scoped_release nogil;
+      const int *d_len = reinterpret_cast<const int *>(lengths_ptr);
+      if (na)
+        HIP_CHECK(hipMemcpyAsync(d_agents_, agents.data(), na * sizeof(u32),
+                                 hipMemcpyHostToDevice, stream_));
+      hipLaunchKernelGGL(k_reply_count, dim3(nblk), dim3(256), 0, stream_,
+                         d_len, total, d_reply_blk_);
+      hipLaunchKernelGGL(k_scan_counts, dim3(1), dim3(256), 4 * sizeof(u32),
+                         stream_, d_reply_blk_, nblk, d_reply_off_);
+      hipLaunchKernelGGL(k_build_replies, dim3(nblk), dim3(256), 0, stream_,
+                         reinterpret_cast<const uint4 *>(headers_ptr),
+                         reinterpret_cast<const int *>(agent_row_ptr), d_len,
+                         total, d_agents_, na, d_reply_off_, rstride,
+                         type_code, priority, flags, timestamp, d_dev_recs_);
+      HIP_CHECK(hipMemcpyAsync(h_reply_m_, d_reply_off_ + nblk, sizeof(u32),
+                               hipMemcpyDeviceToHost, stream_));
+      HIP_CHECK(hipStreamSynchronize(stream_));
+      m = *h_reply_m_;
+      if (m > (u32)total) // cannot happen: at most one reply per row
+        throw std::runtime_error("reply compaction overran its rows");
+      if (m) {
+        HIP_CHECK(hipMemsetAsync(d_bcast_count_, 0, sizeof(u32), stream_));
+        launch_enqueue(d_dev_recs_, reinterpret_cast<const u8 *>(payload_ptr),
+                       (int)m, base);
+        HIP_CHECK(hipStreamSynchronize(stream_));
+      }
+    }
+    count_ = base + (u64)m;
+    if (count_ > g_.num_slots)
+      evict_base_ = count_ - g_.num_slots;
+    return py::make_tuple(base, m);
   }
 
   // Returns the allocation HANDLE (monotonic counter). The pool slot is
@@ -2121,6 +2361,14 @@ private:
       throw std::out_of_range("agent index out of range");
   }
 
+  // row stride of a device-side payload tensor: the bounds of a
+  // delivery's stride
+  void check_row_stride(u32 stride) const {
+    if (stride < 16 || stride > g_.slot_bytes || stride % 16 != 0)
+      throw std::invalid_argument(
+          "stride must be a multiple of 16 in 16..slot_bytes");
+  }
+
   // Streams driven only by event waits accumulate retired-command
   // bookkeeping inside the HIP runtime; the FIRST full
   // hipStreamSynchronize then pays one giant deferred cleanup
@@ -2218,6 +2466,10 @@ private:
   Rec *d_fetch_hdr_{};
   u32 *d_fetch_status_{};
   u8 *d_fetch_pay_{};
+  Rec *d_dev_recs_{};   // sanitised records of the device-resident send
+  u32 *d_reply_blk_{};  // kept rows per 256-row workgroup
+  u32 *d_reply_off_{};  // their exclusive scan, [blocks] = m
+  u32 *h_reply_m_{};
 
   Rec *h_recs_[2] = {};
   u8 *h_pay_[2] = {};
@@ -2630,6 +2882,14 @@ PYBIND11_MODULE(_swarmq, m) {
       .def("get_bitmap", &DeviceQueue::get_bitmap)
       .def("pack_exchange", &DeviceQueue::pack_exchange)
       .def("enqueue_from_ptrs", &DeviceQueue::enqueue_from_ptrs)
+      .def("enqueue_from_device", &DeviceQueue::enqueue_from_device,
+           py::arg("headers_ptr"), py::arg("payload_ptr"), py::arg("n"),
+           py::arg("stride"))
+      .def("reply_from_device", &DeviceQueue::reply_from_device,
+           py::arg("headers_ptr"), py::arg("agent_row_ptr"),
+           py::arg("lengths_ptr"), py::arg("payload_ptr"), py::arg("total"),
+           py::arg("rstride"), py::arg("agents"), py::arg("type_code"),
+           py::arg("priority"), py::arg("flags"), py::arg("timestamp"))
       .def("receive_many", &DeviceQueue::receive_many, py::arg("agents"),
            py::arg("max_per_agent"), py::arg("priority"),
            py::arg("return_seqs") = true)

@@ -23,6 +23,7 @@ import numpy as np
 from ..core.config import QueueConfig
 from .engine import (
     BROADCAST,
+    FLAG_DERIVED_ID,
     NO_BITMAP,
     REC_DTYPE,
     ST_DELETED,
@@ -308,6 +309,35 @@ class CpuEngine(Engine):
     def ack_device(self, seqs, n=None, status=ST_PROCESSED):
         with self._lock:
             super().ack_device(seqs, n, status)
+
+    def _park_failed(self, seqs: np.ndarray) -> np.ndarray:
+        # the stored header of an error-lane record, as k_enqueue_meta
+        # leaves it: no payload. enqueue_batch keeps the caller's lengths
+        # in the header (only the heap length is zeroed), which for a
+        # device-side record would be the OVERSIZE_LEN marker
+        if len(seqs):
+            idx = seqs.astype(np.int64)
+            failed = idx[self._status[idx] == ST_FAILED]
+            self._hdr["payload_len"][failed] = 0
+            self._hdr["content_len"][failed] = 0
+        return seqs
+
+    def enqueue_from_device(self, headers, payload, n=None):
+        with self._lock:
+            return self._park_failed(
+                super().enqueue_from_device(headers, payload, n)
+            )
+
+    def reply_to_device(self, delivery, agent_idxs, payload, lengths,
+                        type_code, priority=None, flags=FLAG_DERIVED_ID,
+                        timestamp=None):
+        with self._lock:
+            return self._park_failed(
+                super().reply_to_device(
+                    delivery, agent_idxs, payload, lengths, type_code,
+                    priority, flags, timestamp,
+                )
+            )
 
     def peek_inbox(self, agent_idx: int) -> np.ndarray:
         with self._lock:

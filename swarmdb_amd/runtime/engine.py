@@ -25,6 +25,7 @@ on GPU). This replaces the reference's per-message produce path
 from __future__ import annotations
 
 import abc
+import time
 from dataclasses import dataclass
 from typing import Any, Dict, List, Optional, Tuple
 
@@ -180,6 +181,79 @@ def check_delivery_out(
                 f"out.{name} holds {len(getattr(out, name))} rows, "
                 f"this call needs {rows}"
             )
+
+
+# payload_len a device-side record is staged with when its length does
+# not fit its payload row: above every slot_bytes, so the enqueue's own
+# validation parks it in the error lane
+OVERSIZE_LEN = 0xFFFFFFFF
+
+
+def check_row_stride(stride: int, slot_bytes: int) -> None:
+    """Row-stride rule of the device-resident planes (ValueError)."""
+    if stride < 16 or stride > slot_bytes or stride % 16:
+        raise ValueError(
+            f"stride {stride} is not a multiple of 16 in 16..{slot_bytes}"
+        )
+
+
+def check_send_arrays(
+    headers: Any, payload: Any, n: Optional[int], slot_bytes: int
+) -> Tuple[np.ndarray, np.ndarray, int, int]:
+    """Host-array form of the :meth:`Engine.enqueue_from_device`
+    arguments: (REC_DTYPE records [cap], uint8 payload [cap, stride], n,
+    stride), or ValueError."""
+    for name, a in (("headers", headers), ("payload", payload)):
+        if not isinstance(a, np.ndarray) or not a.flags.c_contiguous:
+            raise ValueError(f"{name} must be a contiguous numpy array")
+    if headers.dtype == REC_DTYPE and headers.ndim == 1:
+        recs = headers
+    elif (headers.dtype == np.uint8 and headers.ndim == 2
+          and headers.shape[1] == REC_DTYPE.itemsize):
+        recs = headers.view(REC_DTYPE).reshape(-1)
+    else:
+        raise ValueError("headers must be uint8 [cap, 48] or REC_DTYPE [cap]")
+    if payload.dtype != np.uint8 or payload.ndim != 2:
+        raise ValueError("payload must be uint8 [cap, stride]")
+    cap = len(recs)
+    if payload.shape[0] < cap:
+        raise ValueError("payload holds fewer rows than headers")
+    check_row_stride(int(payload.shape[1]), slot_bytes)
+    n = cap if n is None else int(n)
+    if not 0 <= n <= cap:
+        raise ValueError("n must be within 0..cap")
+    return recs, payload, n, int(payload.shape[1])
+
+
+def check_reply_arrays(
+    payload: Any, lengths: Any, total: int, slot_bytes: int
+) -> Tuple[np.ndarray, np.ndarray, int]:
+    """Host-array form of the reply tensors of
+    :meth:`Engine.reply_to_device`: (uint8 payload [>= total, rstride],
+    int32 lengths [>= total], rstride), or ValueError."""
+    for name, a in (("payload", payload), ("lengths", lengths)):
+        if not isinstance(a, np.ndarray) or not a.flags.c_contiguous:
+            raise ValueError(f"{name} must be a contiguous numpy array")
+    if payload.dtype != np.uint8 or payload.ndim != 2:
+        raise ValueError("payload must be uint8 [rows, rstride]")
+    if lengths.dtype != np.int32 or lengths.ndim != 1:
+        raise ValueError("lengths must be int32 [rows]")
+    if payload.shape[0] < total or lengths.shape[0] < total:
+        raise ValueError("payload / lengths hold fewer rows than the delivery")
+    check_row_stride(int(payload.shape[1]), slot_bytes)
+    return payload, lengths, int(payload.shape[1])
+
+
+def check_reply_fields(
+    type_code: int, priority: Optional[int], flags: int
+) -> Tuple[int, int, int]:
+    """(type, priority or -1 for 'inherit', flags) as the one-byte record
+    fields they become, or ValueError."""
+    code, flags = int(type_code), int(flags)
+    prio = -1 if priority is None else int(priority)
+    if not (0 <= code <= 255 and 0 <= flags <= 255 and -1 <= prio <= 255):
+        raise ValueError("type, priority and flags are one byte each")
+    return code, prio, flags
 
 
 class Engine(abc.ABC):
@@ -345,6 +419,110 @@ class Engine(abc.ABC):
             if s < lo or s >= hi or self.get_status(s) == ST_DELETED:
                 continue
             self.set_status(s, int(status))
+
+    # --- device-resident send ---
+
+    def enqueue_from_device(
+        self, headers: Any, payload: Any, n: Optional[int] = None
+    ) -> np.ndarray:
+        """Enqueue the first ``n`` (default: all ``cap``) records of
+        ``headers`` — uint8 ``[cap, 48]`` holding REC_DTYPE records —
+        with row ``i`` of ``payload`` (uint8 ``[cap, stride]``, stride a
+        multiple of 16 in ``16..slot_bytes``) as record ``i``'s payload.
+        Returns the seqs ``base..base+n``. On the GPU engine both are
+        torch tensors in HBM and nothing but the launch crosses PCIe.
+
+        The records are device data the host never sees, so only what
+        the host can bound is followed: a record's own ``payload_off``
+        is ignored, and ``payload_len > stride`` takes the error lane
+        like any malformed record (FAILED, stored ``payload_len ==
+        content_len == 0``, no inbox entry). ``bitmap`` carries the raw
+        :meth:`alloc_bitmap` handle as for :meth:`enqueue_batch`; the GPU
+        engine splits it on the device and overwrites ``bitmap_epoch``.
+        Someone forwarding DELIVERED headers of restricted-visibility
+        messages must restore the handle first (``bitmap =
+        bitmap_epoch``, as ``GpuEngine.unsplit_bitmap_handles`` does).
+        Broadcasts and VIS_GROUP fan out as in any batch. Every refusal
+        (dtype, device, contiguity, alignment, stride, ``n``) is a
+        ValueError raised before anything is enqueued.
+
+        Default: the CPU double on :meth:`enqueue_batch`; it also takes a
+        REC_DTYPE array for ``headers``."""
+        recs, pay, n, stride = check_send_arrays(
+            headers, payload, n, self.cfg.slot_bytes  # type: ignore[attr-defined]
+        )
+        if n == 0:
+            return np.empty(0, dtype=np.uint64)
+        recs = recs[:n].copy()
+        recs["payload_off"] = np.arange(n, dtype=np.uint64) * np.uint64(stride)
+        recs["payload_len"][recs["payload_len"] > stride] = OVERSIZE_LEN
+        recs["bitmap_epoch"] = 0
+        return self.enqueue_batch(recs, pay[:n].tobytes())
+
+    def reply_to_device(
+        self,
+        delivery: DeviceDelivery,
+        agent_idxs: np.ndarray,
+        payload: Any,
+        lengths: Any,
+        type_code: int,
+        priority: Optional[int] = None,
+        flags: int = FLAG_DERIVED_ID,
+        timestamp: Optional[float] = None,
+    ) -> np.ndarray:
+        """Answer the rows of ``delivery`` (polled with ``agent_idxs``)
+        from engine-resident arrays: row ``r < delivery.total`` gets a
+        reply iff ``lengths[r] >= 0`` (int32 ``[>= total]``), with the
+        first ``lengths[r]`` bytes of row ``r`` of ``payload`` (uint8
+        ``[>= total, rstride]``, the stride rules of
+        :meth:`enqueue_from_device`) as payload and content.
+
+        The reply goes from the POLLED agent of the row
+        (``agent_idxs[agent_row[r]]`` — the delivered receiver may be
+        BROADCAST) to the delivered message's sender, with type
+        ``type_code``, ``priority`` (default: the delivered message's),
+        ``flags``, the one ``timestamp`` (default: now), no visibility
+        restriction and ``token_count`` 0. ``lengths[r] > rstride`` takes
+        the error lane. Replies are numbered in row order — the j-th
+        answered row gets ``base + j`` — and their seqs are returned;
+        nothing is enqueued when no row is answered. On the GPU engine
+        the count of replies is the one word that crosses PCIe.
+
+        Default: the CPU double on :meth:`enqueue_batch`."""
+        agent_idxs = np.ascontiguousarray(agent_idxs, dtype=np.uint32)
+        total = int(delivery.total)
+        if len(agent_idxs) != len(delivery.counts):
+            raise ValueError("agent_idxs must be the polled list of the delivery")
+        pay, lens, rstride = check_reply_arrays(
+            payload, lengths, total, self.cfg.slot_bytes  # type: ignore[attr-defined]
+        )
+        code, prio, flags = check_reply_fields(type_code, priority, flags)
+        lens = lens[:total].astype(np.int64)
+        rows = np.flatnonzero(lens >= 0)
+        m = len(rows)
+        if m == 0:
+            return np.empty(0, dtype=np.uint64)
+        hdr = np.ascontiguousarray(_to_numpy(delivery.headers[:total]))
+        if hdr.dtype != REC_DTYPE:
+            hdr = hdr.view(REC_DTYPE).reshape(-1)
+        hdr = hdr[rows]
+        arow = np.asarray(_to_numpy(delivery.agent_row[:total]))[rows]
+        known = (arow >= 0) & (arow < len(agent_idxs))
+        recs = np.zeros(m, dtype=REC_DTYPE)
+        recs["sender"] = BROADCAST  # a row of no polled agent: error lane
+        recs["sender"][known] = agent_idxs[arow[known]]
+        recs["receiver"] = hdr["sender"]
+        recs["type"] = code
+        recs["priority"] = hdr["priority"] if prio < 0 else prio
+        recs["vis_mode"] = VIS_ALL
+        recs["flags"] = flags
+        recs["timestamp"] = time.time() if timestamp is None else timestamp
+        recs["payload_off"] = rows.astype(np.uint64) * np.uint64(rstride)
+        recs["payload_len"] = np.where(lens[rows] > rstride, OVERSIZE_LEN,
+                                       lens[rows])
+        recs["content_len"] = lens[rows]
+        recs["bitmap"] = NO_BITMAP
+        return self.enqueue_batch(recs, pay[:total].tobytes())
 
     @abc.abstractmethod
     def peek_inbox(self, agent_idx: int) -> np.ndarray:

@@ -665,6 +665,62 @@ class SwarmsDB:
             else:
                 self.engine.ack_device(delivery_or_seqs, None, code)
 
+    def send_device(self, headers, payload, n: Optional[int] = None) -> np.ndarray:
+        """Send records that live where the engine keeps them: REC_DTYPE
+        records as uint8 ``[cap, 48]`` plus one payload row each (uint8
+        ``[cap, stride]``) — torch tensors in HBM on the GPU engine,
+        numpy arrays on the CPU engine. The rules (row ownership, error
+        lane, bitmap handles, refusals) are those of
+        :meth:`Engine.enqueue_from_device`. Message ids are derived from
+        (rank, seq), as for :meth:`send_batch`. Returns seqs."""
+        with tracer.span("send_device"):
+            seqs = self.engine.enqueue_from_device(headers, payload, n)
+        self._maybe_autosave()
+        return seqs
+
+    def reply_device(
+        self,
+        delivery: DeviceDelivery,
+        agent_ids: List[str],
+        payload,
+        lengths,
+        message_type: Union[MessageType, str] = MessageType.FUNCTION_RESULT,
+        priority: Union[MessagePriority, int, None] = None,
+    ) -> np.ndarray:
+        """Answer a :meth:`receive_device` delivery without leaving the
+        engine's memory: row ``r`` gets a reply iff ``lengths[r] >= 0``,
+        whose content is the first ``lengths[r]`` bytes of row ``r`` of
+        ``payload`` (raw utf-8; see :meth:`Engine.reply_to_device` for
+        the tensors). ``agent_ids`` is the list the delivery was polled
+        with; each reply goes from the polled agent to the sender of the
+        message it answers, with ``message_type`` and ``priority``
+        (default: the answered message's). Unregistered ids, or a list of
+        another length than the delivery's, raise ValueError before
+        anything is sent. Reply ids are the derived (rank, seq) ids, as
+        for :meth:`send_batch`. Returns the replies' seqs, in row order."""
+        with self._lock:
+            if len(agent_ids) != len(delivery.counts):
+                raise ValueError(
+                    "agent_ids must be the list the delivery was polled with"
+                )
+            unknown = [a for a in agent_ids if a not in self.registered_agents]
+            if unknown:
+                raise ValueError(f"unregistered agents: {unknown}")
+            idxs = np.array(
+                [self._agent_idx[a] for a in agent_ids], dtype=np.uint32
+            )
+        prio = None
+        if priority is not None:
+            prio = (priority if isinstance(priority, MessagePriority)
+                    else MessagePriority(priority)).value
+        with tracer.span("reply_device", n=int(delivery.total)):
+            seqs = self.engine.reply_to_device(
+                delivery, idxs, payload, lengths, _type_code(message_type),
+                prio,
+            )
+        self._maybe_autosave()
+        return seqs
+
     def messages_from_delivery(
         self, delivery: DeviceDelivery
     ) -> List[List[Message]]:

@@ -20,12 +20,15 @@ import numpy as np
 
 from ..core.config import QueueConfig
 from .engine import (
+    FLAG_DERIVED_ID,
     REC_DTYPE,
     ST_DELETED,
     ST_PROCESSED,
     DeviceDelivery,
     Engine,
     check_delivery_out,
+    check_reply_fields,
+    check_row_stride,
     delivery_stride,
 )
 
@@ -345,6 +348,120 @@ class GpuEngine(Engine):
         torch.cuda.current_stream(dev).synchronize()
         with self._lock:
             self.q.ack_device(t.data_ptr(), n, int(status))
+
+    # --- device-resident send ---
+
+    def _check_device_tensor(self, name: str, t, dtype, ndim: int,
+                             align: int) -> None:
+        """Refuse (ValueError) anything but a contiguous, aligned tensor
+        of the given dtype and rank on the queue's GPU."""
+        torch, dev = self._torch_device()
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{name} must be a torch tensor on {dev}")
+        if t.device != dev:
+            raise ValueError(f"{name} is on {t.device}, the queue is on {dev}")
+        if t.dtype != dtype or t.dim() != ndim:
+            raise ValueError(f"{name} must be {dtype} with {ndim} dimension(s)")
+        if not t.is_contiguous():
+            raise ValueError(f"{name} must be contiguous")
+        if t.data_ptr() % align:
+            raise ValueError(f"{name} must be {align}-byte aligned")
+
+    def enqueue_from_device(self, headers, payload, n: Optional[int] = None):
+        """k_stage_device + the enqueue kernels over torch tensors on the
+        queue's GPU (see :meth:`Engine.enqueue_from_device`): no staging
+        copy, nothing but the launches crosses PCIe. The caller's current
+        torch stream is drained first (the tensors may still be being
+        written) and the engine stream is synchronized before return, so
+        the tensors may be overwritten at once."""
+        torch, dev = self._torch_device()
+        self._check_device_tensor("headers", headers, torch.uint8, 2, 16)
+        self._check_device_tensor("payload", payload, torch.uint8, 2, 16)
+        cap = int(headers.shape[0])
+        if headers.shape[1] != REC_DTYPE.itemsize:
+            raise ValueError("headers must be uint8 [cap, 48]")
+        if payload.shape[0] < cap:
+            raise ValueError("payload holds fewer rows than headers")
+        stride = int(payload.shape[1])
+        check_row_stride(stride, self._slot_bytes)
+        n = cap if n is None else int(n)
+        if not 0 <= n <= cap:
+            raise ValueError("n must be within 0..cap")
+        if n == 0:
+            return np.empty(0, dtype=np.uint64)
+        torch.cuda.current_stream(dev).synchronize()
+        hp, pp = headers.data_ptr(), payload.data_ptr()
+        with self._lock:
+            base = done = 0
+            while done < n:
+                chunk = min(self._staging, n - done)
+                b = self.q.enqueue_from_device(
+                    hp + done * REC_DTYPE.itemsize, pp + done * stride,
+                    chunk, stride,
+                )
+                base = b if done == 0 else base
+                done += chunk
+        return np.arange(base, base + n, dtype=np.uint64)
+
+    def reply_to_device(
+        self,
+        delivery: DeviceDelivery,
+        agent_idxs: np.ndarray,
+        payload,
+        lengths,
+        type_code: int,
+        priority: Optional[int] = None,
+        flags: int = FLAG_DERIVED_ID,
+        timestamp: Optional[float] = None,
+    ) -> np.ndarray:
+        """k_build_replies + the enqueue kernels over the delivery's own
+        tensors and the caller's reply tensors (see
+        :meth:`Engine.reply_to_device`). Only the polled agents go to
+        the device and only the reply count comes back (4 B per
+        ``staging_batch`` rows). Stream contract as in
+        :meth:`enqueue_from_device`."""
+        torch, dev = self._torch_device()
+        agent_idxs = np.ascontiguousarray(agent_idxs, dtype=np.uint32)
+        total = int(delivery.total)
+        if len(agent_idxs) != len(delivery.counts):
+            raise ValueError("agent_idxs must be the polled list of the delivery")
+        if len(agent_idxs) and int(agent_idxs.max()) >= self.cfg.max_agents:
+            raise ValueError("agent index out of range")
+        self._check_device_tensor(
+            "delivery.headers", delivery.headers, torch.uint8, 2, 16)
+        self._check_device_tensor(
+            "delivery.agent_row", delivery.agent_row, torch.int32, 1, 4)
+        self._check_device_tensor("payload", payload, torch.uint8, 2, 16)
+        self._check_device_tensor("lengths", lengths, torch.int32, 1, 4)
+        if (delivery.headers.shape[0] < total
+                or delivery.headers.shape[1] != REC_DTYPE.itemsize
+                or delivery.agent_row.shape[0] < total):
+            raise ValueError("delivery tensors hold fewer rows than its total")
+        if payload.shape[0] < total or lengths.shape[0] < total:
+            raise ValueError(
+                "payload / lengths hold fewer rows than the delivery")
+        rstride = int(payload.shape[1])
+        check_row_stride(rstride, self._slot_bytes)
+        code, prio, flags = check_reply_fields(type_code, priority, flags)
+        ts = time.time() if timestamp is None else float(timestamp)
+        if total == 0:
+            return np.empty(0, dtype=np.uint64)
+        torch.cuda.current_stream(dev).synchronize()
+        hp, rp = delivery.headers.data_ptr(), delivery.agent_row.data_ptr()
+        lp, pp = lengths.data_ptr(), payload.data_ptr()
+        with self._lock:
+            base = m = done = 0
+            while done < total:
+                chunk = min(self._staging, total - done)
+                b, mc = self.q.reply_from_device(
+                    hp + done * REC_DTYPE.itemsize, rp + done * 4,
+                    lp + done * 4, pp + done * rstride, chunk, rstride,
+                    agent_idxs, code, prio, flags, ts,
+                )
+                base = b if done == 0 else base
+                m += int(mc)
+                done += chunk
+        return np.arange(base, base + m, dtype=np.uint64)
 
     def peek_inbox(self, agent_idx: int) -> np.ndarray:
         _, entries = self.q.inbox_window(int(agent_idx))
