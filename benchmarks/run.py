@@ -17,9 +17,14 @@
                    message is answered from a device tensor
                    (reply_to_device); --host-return answers through the
                    host instead (D2H, host records, enqueue_batch)
+ 12 dispatch-device config 10's tick plus the token-weighted dispatch of
+                   the delivered rows to 8 LLM backends on the device
+                   (dispatch_delivery / release_dispatch);
+                   --host-dispatch does it through the host instead
+                   (headers D2H, numpy/Python, row lists H2D)
 
 Usage:
-  python -m benchmarks.run --config {1,2,3,5,10,11} [--seconds S]
+  python -m benchmarks.run --config {1,2,3,5,10,11,12} [--seconds S]
   python -m torch.distributed.run --nproc-per-node N benchmarks/run.py --config 4
 
 Each config prints one JSON line:
@@ -297,6 +302,106 @@ def config11_device_echo(seconds: float, host_return: bool = False) -> None:
     _emit(11, "p2p-gpu-1kb-echo", n, elapsed, float(np.median(lat) * 1000),
           {"return": "host" if host_return else "device",
            "stride": state["d"].stride})
+
+
+def _host_dispatch(eng, d, n_backends: int, dev):
+    """The only dispatch there was before dispatch_delivery: headers to
+    the host, the greedy token-weighted choice and the grouping in
+    numpy/Python, the per-backend row lists back to the device. Returns
+    (backend per row, row-list tensors, per-backend counts, added)."""
+    import torch
+
+    t = d.total
+    hdr = d.headers[:t].cpu().numpy().view(REC_DTYPE).reshape(-1)
+    cost = np.maximum(hdr["token_count"].astype(np.int64), 1).tolist()
+    load = eng.backend_loads()[:n_backends].tolist()
+    added = [0] * n_backends
+    backend = np.empty(t, dtype=np.int32)
+    for r in range(t):
+        k = load.index(min(load))
+        load[k] += cost[r]
+        added[k] += cost[r]
+        backend[r] = k
+    order = np.argsort(backend, kind="stable").astype(np.int32)
+    counts = np.bincount(backend, minlength=n_backends).astype(np.int64)
+    lists = torch.from_numpy(order).to(dev).split(counts.tolist())
+    for k in range(n_backends):
+        eng.backend_add_load(k, added[k])
+    return backend, lists, counts, added
+
+
+def config12_device_dispatch(seconds: float, host_dispatch: bool = False) -> None:
+    """Config 10's tick (enqueue_batch -> receive_to_device -> ack_device,
+    4096 x 1 KB) plus the dispatch of the delivered rows to 8 LLM
+    backends by token count and the release of that load: on the device
+    (dispatch_delivery / release_dispatch, buffers reused, 32 B of counts
+    come back), or with ``host_dispatch`` through the host (headers D2H,
+    greedy choice and grouping in numpy/Python, row lists H2D)."""
+    import torch  # before GpuEngine: torch's HIP runtime first
+
+    from swarmdb_amd.runtime.cpu_engine import CpuEngine
+    from swarmdb_amd.runtime.gpu_engine import GpuEngine
+
+    cfg = QueueConfig(use_gpu=True, auto_save=False, max_agents=64,
+                      num_slots=1 << 20, staging_batch=16384)
+    eng = GpuEngine(cfg)
+    eng.register_agent(0)
+    eng.register_agent(1)
+    rng = np.random.default_rng(0)
+    batch = 4096  # one dequeue window, as in config 2
+    nb = 8
+    recs, payload = _make_batch(rng, batch, np.array([0]), np.array([1]), 1024)
+    recs["token_count"] = np.random.default_rng(12).integers(
+        1, 4097, batch, dtype=np.uint32)
+    agents = np.array([1], dtype=np.uint32)
+    state = {"d": None, "disp": None, "backend": None}
+
+    def tick():
+        eng.enqueue_batch(recs, payload)
+        d = state["d"] = eng.receive_to_device(
+            agents, batch, max_payload=1024, out=state["d"])
+        if host_dispatch:
+            backend, _, counts, added = _host_dispatch(
+                eng, d, nb, d.headers.device)
+            for k in range(nb):
+                eng.backend_add_load(k, -added[k])
+            state["backend"] = backend
+        else:
+            disp = state["disp"] = eng.dispatch_delivery(
+                d, nb, weight="tokens", out=state["disp"])
+            counts = disp.counts
+            eng.release_dispatch(disp)
+        eng.ack_device(d.seqs, n=d.total)
+        assert d.total == batch, "device tick failed to drain"
+        assert int(counts.sum()) == batch, "dispatch lost rows"
+        return d.total
+
+    lat = []
+    n = 0
+    for _ in range(3):  # warmup
+        tick()
+    t0 = time.perf_counter()
+    while time.perf_counter() - t0 < seconds:
+        s = time.perf_counter()
+        n += tick()
+        lat.append(time.perf_counter() - s)
+    elapsed = time.perf_counter() - t0
+    # the last tick's choices against the CPU double (outside the timed
+    # region): the same headers, from the loads the tick started with
+    if not host_dispatch:
+        state["backend"] = state["disp"].to_host().backend
+    twin = CpuEngine(QueueConfig(use_gpu=False, auto_save=False, max_agents=64))
+    start = eng.backend_loads()
+    for k in range(nb):
+        twin.backend_add_load(k, int(start[k]))
+    want = twin.dispatch_delivery(state["d"].to_host(), nb, weight="tokens")
+    assert np.array_equal(state["backend"], want.backend[:batch]), \
+        "dispatch differs from the CPU double"
+    eng.close()
+    _emit(12, "p2p-gpu-1kb-device-dispatch", n, elapsed,
+          float(np.median(lat) * 1000),
+          {"dispatch": "host" if host_dispatch else "device",
+           "backends": nb, "weight": "tokens"})
 
 
 def config3_group_fanout(seconds: float) -> None:
@@ -705,10 +810,12 @@ def config5_loadbalancer(seconds: float) -> None:
 def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", type=int, required=True,
-                    choices=[1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11])
+                    choices=[1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12])
     ap.add_argument("--seconds", type=float, default=5.0)
     ap.add_argument("--host-return", action="store_true",
                     help="config 11: send the replies through the host")
+    ap.add_argument("--host-dispatch", action="store_true",
+                    help="config 12: dispatch through the host")
     args = ap.parse_args()
     if args.config == 1:
         config1_cpu_loopback(args.seconds)
@@ -743,6 +850,8 @@ def main() -> int:
         config10_device_delivery(args.seconds)
     elif args.config == 11:
         config11_device_echo(args.seconds, args.host_return)
+    elif args.config == 12:
+        config12_device_dispatch(args.seconds, args.host_dispatch)
     return 0
 
 

@@ -12,7 +12,7 @@ persistence.
 
 from .core.config import QueueConfig
 from .core.message import Message, MessagePriority, MessageStatus, MessageType
-from .runtime.engine import DeviceDelivery
+from .runtime.engine import DeviceDelivery, DeviceDispatch
 from .runtime.facade import SwarmsDB
 
 __version__ = "0.2.0"
@@ -25,4 +25,5 @@ __all__ = [
     "MessagePriority",
     "MessageStatus",
     "DeviceDelivery",
+    "DeviceDispatch",
 ]

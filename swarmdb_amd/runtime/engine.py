@@ -156,6 +156,123 @@ class DeviceDelivery:
         )
 
 
+@dataclass
+class DeviceDispatch:
+    """The rows of a :class:`DeviceDelivery` dispatched to LLM backends
+    (:meth:`Engine.dispatch_delivery`). On the GPU engine every array but
+    ``counts`` is a ``torch.Tensor`` in HBM on the queue's device; on the
+    CPU engine they are numpy arrays with the same dtypes. ``counts`` is
+    the one thing the GPU engine brings to the host (``4 * n_backends``
+    bytes).
+
+    - ``backend``  int32 [rows]  chosen backend per row, ``-1`` for a row
+      the type filter skipped; defined for ``[0, total)``
+    - ``order``    int32 [rows]  the dispatched rows grouped by backend, in
+      row order within a backend; defined for ``[0, m)``
+    - ``offsets``  int32 [n_backends + 1]  exclusive prefix sum:
+      ``order[offsets[k]:offsets[k+1]]`` are backend ``k``'s rows,
+      ``offsets[n_backends] == m``
+    - ``added``    int64 [n_backends]  load this dispatch put on each backend
+    - ``counts``   host int64 [n_backends]  rows per backend
+    - ``rank``     int32 [rows]  scratch: a row's position within its backend
+
+    ``backend[total:]``, ``order[m:]`` and ``rank`` past ``total`` are
+    unspecified. ``released`` is set by :meth:`Engine.release_dispatch`;
+    ``backend_ids`` (the backend names in index order) by the facade.
+    """
+
+    backend: Any
+    order: Any
+    offsets: Any
+    added: Any
+    counts: Any
+    rank: Any
+    n_backends: int
+    total: int
+    m: int
+    released: bool = False
+    backend_ids: Optional[List[str]] = None
+
+    def to_host(self) -> "DeviceDispatch":
+        """Copy with numpy arrays, trimmed to the defined ranges."""
+        return DeviceDispatch(
+            backend=_to_numpy(self.backend[: self.total]),
+            order=_to_numpy(self.order[: self.m]),
+            offsets=_to_numpy(self.offsets[: self.n_backends + 1]),
+            added=_to_numpy(self.added[: self.n_backends]),
+            counts=_to_numpy(self.counts),
+            rank=_to_numpy(self.rank[: self.total]),
+            n_backends=self.n_backends,
+            total=self.total,
+            m=self.m,
+            released=self.released,
+            backend_ids=self.backend_ids,
+        )
+
+
+MAX_DISPATCH_BACKENDS = 64  # one wavefront lane per backend
+
+DISPATCH_WEIGHTS = ("requests", "tokens")
+
+
+def check_dispatch_args(
+    n_backends: int,
+    num_backends: int,
+    weight: str,
+    type_code: Optional[int],
+    pinned: Any,
+    n_agents: int,
+) -> Tuple[int, bool, int, Optional[np.ndarray]]:
+    """(n_backends, by_tokens, type code or -1 for 'no filter', pinned as
+    int32 [n_agents] or None) of :meth:`Engine.dispatch_delivery`, or
+    ValueError."""
+    nb = int(n_backends)
+    if not 1 <= nb <= min(MAX_DISPATCH_BACKENDS, int(num_backends)):
+        raise ValueError(
+            f"n_backends must be within 1.."
+            f"{min(MAX_DISPATCH_BACKENDS, int(num_backends))}"
+        )
+    if weight not in DISPATCH_WEIGHTS:
+        raise ValueError(f"weight must be one of {DISPATCH_WEIGHTS}")
+    code = -1
+    if type_code is not None:
+        code = int(type_code)
+        if not 0 <= code <= 255:
+            raise ValueError("type_code is one byte")
+    pins = None
+    if pinned is not None:
+        raw = np.asarray(pinned)
+        if raw.ndim != 1 or len(raw) != n_agents:
+            raise ValueError(
+                "pinned must hold one entry per polled agent of the delivery"
+            )
+        if raw.dtype.kind not in "iu":
+            raise ValueError("pinned must be an integer array")
+        if len(raw) and (raw.min() < -1 or raw.max() >= nb):
+            raise ValueError(f"pinned entries must be within -1..{nb - 1}")
+        pins = np.ascontiguousarray(raw, dtype=np.int32)
+    return nb, weight == "tokens", code, pins
+
+
+def check_dispatch_out(out: "DeviceDispatch", n_backends: int, total: int) -> None:
+    """Refuse (ValueError) a reused dispatch built for another
+    ``n_backends`` or with fewer than ``total`` rows."""
+    if not isinstance(out, DeviceDispatch):
+        raise ValueError("out must be a DeviceDispatch")
+    if out.n_backends != n_backends or len(out.offsets) != n_backends + 1 \
+            or len(out.added) != n_backends:
+        raise ValueError(
+            f"out was built for {out.n_backends} backends, "
+            f"this call needs {n_backends}"
+        )
+    for name in ("backend", "order", "rank"):
+        if len(getattr(out, name)) < total:
+            raise ValueError(
+                f"out.{name} holds {len(getattr(out, name))} rows, "
+                f"this call needs {total}"
+            )
+
+
 def delivery_stride(max_payload: int, slot_bytes: int) -> int:
     """Row stride of a device-resident delivery: ``max_payload`` rounded up
     to 16 B when it tightens the row below ``slot_bytes``."""
@@ -648,6 +765,135 @@ class Engine(abc.ABC):
             self.backend_add_load(b, 1)
             out[i] = b
         return out
+
+    # --- device-resident dispatch ---
+
+    def dispatch_delivery(
+        self,
+        delivery: DeviceDelivery,
+        n_backends: int,
+        weight: str = "requests",
+        type_code: Optional[int] = None,
+        pinned: Any = None,
+        out: Optional[DeviceDispatch] = None,
+    ) -> DeviceDispatch:
+        """Dispatch the rows of ``delivery`` to ``n_backends`` LLM backends
+        where the engine keeps them. Rows ``r = 0 .. total-1`` are taken in
+        row order against the per-backend load counters of
+        :meth:`backend_add_load` / :meth:`dispatch_batch` (int64, compared
+        as signed)::
+
+            if type_code is not None and header[r].type != type_code:
+                backend[r] = -1                  # row not dispatched
+                continue
+            cost = 1 if weight == "requests" else max(token_count[r], 1)
+            b = agent_row[r]
+            p = pinned[b] if pinned is not None and 0 <= b < na else -1
+            k = p if p >= 0 else argmin(load[0:n_backends])  # ties: lowest
+            load[k] += cost;  added[k] += cost;  backend[r] = k
+
+        ``pinned`` is a host int32 array, one entry per polled agent of
+        the delivery: ``-1`` or a backend index. ``agent_row`` and
+        ``headers`` may have been written to by the consumer: an
+        ``agent_row`` outside the polled list means "not pinned" and is
+        never used as an index; ``type`` and ``token_count`` are values.
+        The result (see :class:`DeviceDispatch`) stays in engine memory;
+        on the GPU engine only the per-backend row counts cross PCIe.
+        ``out`` reuses the buffers of an earlier dispatch. With
+        ``weight="requests"`` and neither filter nor pins,
+        ``backend[:total]`` equals ``dispatch_batch(total, n_backends)``.
+        Hand the result to :meth:`release_dispatch` when the batch is done.
+
+        Every refusal (``n_backends`` outside ``1..min(64, num_backends)``,
+        an unknown ``weight``, a ``type_code`` outside one byte, a
+        ``pinned`` of the wrong length or range, unusable arrays, an
+        ``out`` that is too small or built for another ``n_backends``) is
+        a ValueError raised before any load changes.
+
+        Default: the CPU double, a numpy loop over :meth:`backend_loads`
+        applied through :meth:`backend_add_load`."""
+        na = len(delivery.counts)
+        total = int(delivery.total)
+        nb, by_tokens, code, pins = check_dispatch_args(
+            n_backends, self.cfg.num_backends,  # type: ignore[attr-defined]
+            weight, type_code, pinned, na,
+        )
+        hdr, arow = delivery.headers, delivery.agent_row
+        for name, a in (("delivery.headers", hdr), ("delivery.agent_row", arow)):
+            if not isinstance(a, np.ndarray) or not a.flags.c_contiguous:
+                raise ValueError(f"{name} must be a contiguous numpy array")
+        if hdr.dtype == np.uint8 and hdr.ndim == 2 \
+                and hdr.shape[1] == REC_DTYPE.itemsize:
+            hdr = hdr.view(REC_DTYPE).reshape(-1)
+        elif not (hdr.dtype == REC_DTYPE and hdr.ndim == 1):
+            raise ValueError(
+                "delivery.headers must be uint8 [rows, 48] or REC_DTYPE [rows]")
+        if arow.dtype != np.int32 or arow.ndim != 1:
+            raise ValueError("delivery.agent_row must be int32 [rows]")
+        if len(hdr) < total or len(arow) < total:
+            raise ValueError("delivery arrays hold fewer rows than its total")
+        if out is not None:
+            check_dispatch_out(out, nb, total)
+            for name in ("backend", "order", "rank", "offsets", "added"):
+                if not isinstance(getattr(out, name), np.ndarray):
+                    raise ValueError(f"out.{name} must be a numpy array")
+            backend, order, rank = out.backend, out.order, out.rank
+            offsets, added = out.offsets, out.added
+        else:
+            rows = len(arow)
+            backend = np.zeros(rows, dtype=np.int32)
+            order = np.zeros(rows, dtype=np.int32)
+            rank = np.zeros(rows, dtype=np.int32)
+            offsets = np.zeros(nb + 1, dtype=np.int32)
+            added = np.zeros(nb, dtype=np.int64)
+
+        load = np.asarray(self.backend_loads(), dtype=np.int64)[:nb].copy()
+        types = hdr["type"][:total]
+        tokens = hdr["token_count"][:total].astype(np.int64)
+        cost = np.maximum(tokens, 1) if by_tokens else np.ones(total, np.int64)
+        add = np.zeros(nb, dtype=np.int64)
+        cnt = np.zeros(nb, dtype=np.int64)
+        for r in range(total):
+            if code >= 0 and int(types[r]) != code:
+                backend[r] = -1
+                rank[r] = 0
+                continue
+            b = int(arow[r])
+            k = int(pins[b]) if pins is not None and 0 <= b < na else -1
+            if k < 0:
+                k = int(np.argmin(load))
+            load[k] += cost[r]
+            add[k] += cost[r]
+            backend[r] = k
+            rank[r] = cnt[k]
+            cnt[k] += 1
+        m = int(cnt.sum())
+        chosen = backend[:total]
+        rows_of = np.flatnonzero(chosen >= 0)
+        order[:m] = rows_of[np.argsort(chosen[rows_of], kind="stable")]
+        offsets[0] = 0
+        offsets[1:] = np.cumsum(cnt)
+        added[:] = add
+        for k in range(nb):
+            if add[k]:
+                self.backend_add_load(k, int(add[k]))
+        return DeviceDispatch(
+            backend=backend, order=order, offsets=offsets, added=added,
+            counts=cnt, rank=rank, n_backends=nb, total=total, m=m,
+        )
+
+    def release_dispatch(self, dispatch: DeviceDispatch) -> None:
+        """Take the load of a finished dispatch off its backends:
+        ``load[k] -= added[k]`` — the batch form of completing requests
+        one by one. A second release of the same object is a
+        ValueError."""
+        if dispatch.released:
+            raise ValueError("dispatch was already released")
+        added = np.asarray(_to_numpy(dispatch.added), dtype=np.int64)
+        for k in range(int(dispatch.n_backends)):
+            if added[k]:
+                self.backend_add_load(k, -int(added[k]))
+        dispatch.released = True
 
     # --- lifecycle ---
 

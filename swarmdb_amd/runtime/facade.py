@@ -62,6 +62,7 @@ from .engine import (
     VIS_BITMAP,
     VIS_GROUP,
     DeviceDelivery,
+    DeviceDispatch,
     Engine,
 )
 
@@ -720,6 +721,65 @@ class SwarmsDB:
             )
         self._maybe_autosave()
         return seqs
+
+    def dispatch_device(
+        self,
+        delivery: DeviceDelivery,
+        agent_ids: List[str],
+        weight: str = "requests",
+        message_type: Union[MessageType, str, None] = None,
+    ) -> DeviceDispatch:
+        """Dispatch the rows of a :meth:`receive_device` delivery to the
+        registered LLM backends without leaving the engine's memory — the
+        batch form of :meth:`dispatch_llm_request`. Each row goes to the
+        least-loaded backend, costing 1 (``weight="requests"``) or its
+        ``token_count`` (``weight="tokens"``); with ``message_type`` only
+        rows of that type are dispatched. While ``llm_load_balancing`` is
+        off, the rows of an agent with an assigned backend
+        (:meth:`assign_llm_backend`) go to that backend; when it is on,
+        nothing is pinned. ``agent_ids`` is the list the delivery was
+        polled with; unregistered ids, or a list of another length than
+        the delivery's, raise ValueError, and no registered backend is a
+        RuntimeError, before any load changes. The result (see
+        :class:`DeviceDispatch`) carries ``backend_ids``, the backend
+        names in index order; hand it to :meth:`complete_device` when the
+        batch is done."""
+        with self._lock:
+            n = len(self._llm_backends)
+            if n == 0:
+                raise RuntimeError("no LLM backends registered")
+            if len(agent_ids) != len(delivery.counts):
+                raise ValueError(
+                    "agent_ids must be the list the delivery was polled with"
+                )
+            unknown = [a for a in agent_ids if a not in self.registered_agents]
+            if unknown:
+                raise ValueError(f"unregistered agents: {unknown}")
+            pinned = None
+            if not self.llm_load_balancing:
+                assigned = self.metadata.get("llm_backends", {})
+                pinned = np.array(
+                    [self._llm_backend_idx.get(assigned.get(a), -1)
+                     for a in agent_ids],
+                    dtype=np.int32,
+                )
+                if not (pinned >= 0).any():
+                    pinned = None
+            names = list(self._llm_backends)
+        code = None if message_type is None else _type_code(message_type)
+        with tracer.span("dispatch_device", n=int(delivery.total)):
+            d = self.engine.dispatch_delivery(
+                delivery, n, weight, code, pinned
+            )
+        d.backend_ids = names
+        return d
+
+    def complete_device(self, dispatch: DeviceDispatch) -> None:
+        """Take the load of a finished :meth:`dispatch_device` batch off
+        its backends — the batch form of :meth:`complete_llm_request`. A
+        second call with the same dispatch raises ValueError."""
+        with tracer.span("complete_device"):
+            self.engine.release_dispatch(dispatch)
 
     def messages_from_delivery(
         self, delivery: DeviceDelivery

@@ -21,18 +21,24 @@ import numpy as np
 from ..core.config import QueueConfig
 from .engine import (
     FLAG_DERIVED_ID,
+    MAX_DISPATCH_BACKENDS,
     REC_DTYPE,
     ST_DELETED,
     ST_PROCESSED,
     DeviceDelivery,
+    DeviceDispatch,
     Engine,
     check_delivery_out,
+    check_dispatch_args,
+    check_dispatch_out,
     check_reply_fields,
     check_row_stride,
     delivery_stride,
 )
 
 _FETCH_DTYPE = np.dtype(REC_DTYPE.descr + [("status", np.uint8), ("seq", np.uint64)])
+
+_NO_PINS = np.empty(0, dtype=np.int32)  # dispatch_delivery without pins
 
 
 def _load_ext():
@@ -739,6 +745,90 @@ class GpuEngine(Engine):
         return np.asarray(
             self.q.lb_dispatch(int(requests), int(n_backends)), dtype=np.uint32
         )
+
+    # --- device-resident dispatch ---
+
+    def dispatch_delivery(
+        self,
+        delivery: DeviceDelivery,
+        n_backends: int,
+        weight: str = "requests",
+        type_code: Optional[int] = None,
+        pinned=None,
+        out: Optional[DeviceDispatch] = None,
+    ) -> DeviceDispatch:
+        """k_dispatch_rows + k_dispatch_scatter over the delivery's own
+        tensors (see :meth:`Engine.dispatch_delivery`): the serial greedy
+        walk runs in one wavefront on the balancer's stream, the result
+        stays in torch tensors on the queue's GPU. Only ``pinned`` goes to
+        the device and only the per-backend row counts come back. The
+        caller's current torch stream is drained first (the delivery's
+        tensors may still be being written) and the balancer's stream is
+        synchronized before return."""
+        torch, dev = self._torch_device()
+        na = len(delivery.counts)
+        total = int(delivery.total)
+        nb, by_tokens, code, pins = check_dispatch_args(
+            n_backends, self.cfg.num_backends, weight, type_code, pinned, na
+        )
+        if na > self.cfg.max_agents:
+            raise ValueError("more polled agents than max_agents")
+        self._check_device_tensor(
+            "delivery.headers", delivery.headers, torch.uint8, 2, 16)
+        self._check_device_tensor(
+            "delivery.agent_row", delivery.agent_row, torch.int32, 1, 4)
+        if (delivery.headers.shape[0] < total
+                or delivery.headers.shape[1] != REC_DTYPE.itemsize
+                or delivery.agent_row.shape[0] < total):
+            raise ValueError("delivery tensors hold fewer rows than its total")
+        if out is not None:
+            check_dispatch_out(out, nb, total)
+            for name in ("backend", "order", "rank", "offsets"):
+                self._check_device_tensor(
+                    f"out.{name}", getattr(out, name), torch.int32, 1, 4)
+            self._check_device_tensor("out.added", out.added, torch.int64, 1, 8)
+            backend, order, rank = out.backend, out.order, out.rank
+            offsets, added = out.offsets, out.added
+        else:
+            rows = int(delivery.agent_row.shape[0])
+            backend = torch.empty(rows, dtype=torch.int32, device=dev)
+            order = torch.empty(rows, dtype=torch.int32, device=dev)
+            rank = torch.empty(rows, dtype=torch.int32, device=dev)
+            offsets = torch.empty(nb + 1, dtype=torch.int32, device=dev)
+            added = torch.empty(nb, dtype=torch.int64, device=dev)
+        torch.cuda.current_stream(dev).synchronize()
+        with self._lock:
+            counts = self.q.dispatch_from_device(
+                delivery.headers.data_ptr(), delivery.agent_row.data_ptr(),
+                total, pins if pins is not None else _NO_PINS,
+                pins is not None, nb, code, by_tokens,
+                backend.data_ptr(), rank.data_ptr(), order.data_ptr(),
+                offsets.data_ptr(), added.data_ptr(),
+            )
+        counts = np.asarray(counts, dtype=np.int64)
+        return DeviceDispatch(
+            backend=backend, order=order, offsets=offsets, added=added,
+            counts=counts, rank=rank, n_backends=nb, total=total,
+            m=int(counts.sum()),
+        )
+
+    def release_dispatch(self, dispatch: DeviceDispatch) -> None:
+        """k_release_loads over the dispatch's own ``added`` tensor, on
+        the balancer's stream (see :meth:`Engine.release_dispatch`)."""
+        torch, dev = self._torch_device()
+        if dispatch.released:
+            raise ValueError("dispatch was already released")
+        nb = int(dispatch.n_backends)
+        if not 1 <= nb <= min(MAX_DISPATCH_BACKENDS, self.cfg.num_backends):
+            raise ValueError("dispatch has an unusable n_backends")
+        self._check_device_tensor(
+            "dispatch.added", dispatch.added, torch.int64, 1, 8)
+        if dispatch.added.shape[0] != nb:
+            raise ValueError("dispatch.added must hold n_backends entries")
+        torch.cuda.current_stream(dev).synchronize()
+        with self._lock:
+            self.q.release_dispatch(dispatch.added.data_ptr(), nb)
+        dispatch.released = True
 
     # --- lifecycle ---
 
