@@ -22,9 +22,15 @@
                    (dispatch_delivery / release_dispatch);
                    --host-dispatch does it through the host instead
                    (headers D2H, numpy/Python, row lists H2D)
+ 13 context-device config 10's tick over a pre-filled log in which 64
+                   agent pairs keep a dialogue, plus the conversation
+                   context of every delivered row gathered on the device
+                   (context_to_device, depth 8, lookback 65536);
+                   --host-context builds it through the host instead (two
+                   queries per (agent, sender) pair, fetch, numpy, H2D)
 
 Usage:
-  python -m benchmarks.run --config {1,2,3,5,10,11,12} [--seconds S]
+  python -m benchmarks.run --config {1,2,3,5,10,11,12,13} [--seconds S]
   python -m torch.distributed.run --nproc-per-node N benchmarks/run.py --config 4
 
 Each config prints one JSON line:
@@ -402,6 +408,154 @@ def config12_device_dispatch(seconds: float, host_dispatch: bool = False) -> Non
           float(np.median(lat) * 1000),
           {"dispatch": "host" if host_dispatch else "device",
            "backends": nb, "weight": "tokens"})
+
+
+def _host_context(eng, d, agents, depth: int, per_agent: int, host, ctx):
+    """The only conversation context there was before context_to_device:
+    per distinct (agent, sender) pair of the tick two ``query`` calls (the
+    get_conversation path), a gather of the candidates to the host, the
+    per-row choice of the newest ``depth`` below the row's own seq in
+    numpy, and one H2D copy per array into the layout of DeviceContext.
+    A direction's newest ``depth + per_agent`` hold every candidate of a
+    row: at most ``per_agent`` of them are of this tick. ``host`` are the
+    pinned staging tensors, ``ctx`` the device tensors written."""
+    t = d.total
+    hdr = d.headers[:t].cpu().numpy().view(REC_DTYPE).reshape(-1)
+    seqs = d.seqs[:t].cpu().numpy()
+    a_of = agents[d.agent_row[:t].cpu().numpy()].astype(np.int64)
+    s_of = hdr["sender"].astype(np.int64)
+    stride = ctx.stride
+    h_counts, h_seqs, h_len, h_hdr, h_pay = (x.numpy() for x in host)
+    h_counts[:t] = 0
+    h_seqs[:t] = -1
+    h_len[:t] = 0
+    recs_out = h_hdr.view(REC_DTYPE).reshape(h_hdr.shape[0], depth)
+    limit = depth + per_agent
+    slot = np.arange(depth, dtype=np.int64)
+    for key in np.unique(a_of * (1 << 32) + s_of).tolist():
+        a, s = key >> 32, key & 0xFFFFFFFF
+        found = [eng.query(sender=s, receiver=a, limit=limit)]
+        if a != s:
+            found.append(eng.query(sender=a, receiver=s, limit=limit))
+        q = np.unique(np.concatenate(found)).astype(np.int64)
+        if len(q) == 0:
+            continue
+        hdrs, flat, fstride = eng.fetch_raw_chunks(q.astype(np.uint64))
+        flat = flat.reshape(len(q), fstride)[:, :stride]
+        rows = np.flatnonzero((a_of == a) & (s_of == s))
+        end = np.searchsorted(q, seqs[rows])  # candidates below the row
+        cnt = np.minimum(end, depth)
+        idx = (end - cnt)[:, None] + slot[None, :]
+        live = slot[None, :] < cnt[:, None]
+        rr = np.broadcast_to(rows[:, None], idx.shape)[live]
+        jj = np.broadcast_to(slot[None, :], idx.shape)[live]
+        src = idx[live]
+        h_counts[rows] = cnt
+        h_seqs[rr, jj] = q[src]
+        lens = np.minimum(hdrs["payload_len"][src], stride).astype(np.int32)
+        h_len[rr, jj] = lens
+        pay = flat[src]
+        pay[np.arange(stride)[None, :] >= lens[:, None]] = 0
+        h_pay[rr, jj] = pay
+        out = np.zeros(len(src), dtype=REC_DTYPE)
+        for name in REC_DTYPE.names:
+            out[name] = hdrs[name][src]
+        out["payload_off"] = (rr * depth + jj).astype(np.uint64) \
+            * np.uint64(stride)
+        recs_out[rr, jj] = out
+    for dst, src_t in zip((ctx.counts, ctx.seqs, ctx.lengths, ctx.headers,
+                           ctx.payload), host):
+        dst[:t].copy_(src_t[:t])
+
+
+def config13_device_context(seconds: float, host_context: bool = False) -> None:
+    """Config 10's tick (enqueue_batch -> receive_to_device -> ack_device,
+    4096 x 1 KB) over a pre-filled log in which 64 agent pairs keep a
+    running dialogue, plus the conversation context of every delivered row
+    (depth 8 within a lookback of 65536): on the device
+    (context_to_device, buffers reused, nothing comes back), or with
+    ``host_context`` through the host (two queries per distinct (agent,
+    sender) pair, candidates gathered D2H, rows packed in numpy, H2D into
+    the same layout). The last tick's context is compared with the CPU
+    double run over the same log."""
+    import torch  # before GpuEngine: torch's HIP runtime first
+
+    from swarmdb_amd.runtime.engine import DeviceContext, Engine
+    from swarmdb_amd.runtime.gpu_engine import GpuEngine
+
+    pairs, depth, lookback = 64, 8, 65536
+    na = 2 * pairs
+    cfg = QueueConfig(use_gpu=True, auto_save=False, max_agents=na,
+                      num_slots=1 << 20, staging_batch=16384)
+    eng = GpuEngine(cfg)
+    for a in range(na):
+        eng.register_agent(a)
+    rng = np.random.default_rng(0)
+    batch = 4096  # config 10's tick
+    per_agent = batch // na
+    recs, payload = _make_batch(rng, batch, np.array([0]), np.array([1]), 1024)
+    # message i belongs to pair i % 64 and alternates direction, so every
+    # agent gets batch / 128 messages per tick, all from its partner
+    i = np.arange(batch)
+    p, flip = i % pairs, (i // pairs) % 2
+    recs["sender"] = 2 * p + flip
+    recs["receiver"] = 2 * p + 1 - flip
+    agents = np.arange(na, dtype=np.uint32)
+    state = {"d": None, "ctx": None}
+    host = None
+
+    def tick(context=True):
+        eng.enqueue_batch(recs, payload)
+        d = state["d"] = eng.receive_to_device(
+            agents, per_agent, max_payload=1024, out=state["d"])
+        if context and host_context:
+            _host_context(eng, d, agents, depth, per_agent, host, state["ctx"])
+        elif context:
+            state["ctx"] = eng.context_to_device(
+                d, agents, depth, lookback, max_payload=1024,
+                out=state["ctx"])
+        eng.ack_device(d.seqs, n=d.total)
+        assert d.total == batch, "device tick failed to drain"
+        return d.total
+
+    for _ in range(lookback // batch):  # pre-fill: a lookback of dialogue
+        tick(context=False)
+    if host_context:
+        dev = state["d"].seqs.device
+        rows, stride = batch, state["d"].stride
+        shapes = (((rows,), torch.int32), ((rows, depth), torch.int64),
+                  ((rows, depth), torch.int32),
+                  ((rows, depth, REC_DTYPE.itemsize), torch.uint8),
+                  ((rows, depth, stride), torch.uint8))
+        host = [torch.zeros(s, dtype=t, pin_memory=True) for s, t in shapes]
+        state["ctx"] = DeviceContext(
+            *(torch.zeros(s, dtype=t, device=dev) for s, t in shapes),
+            depth=depth, stride=stride, total=batch)
+    lat = []
+    n = 0
+    for _ in range(3):  # warmup
+        tick()
+    t0 = time.perf_counter()
+    while time.perf_counter() - t0 < seconds:
+        s = time.perf_counter()
+        n += tick()
+        lat.append(time.perf_counter() - s)
+    elapsed = time.perf_counter() - t0
+    # the last tick's context against the CPU double over the same log
+    # (outside the timed region)
+    got = state["ctx"].to_host()
+    want = Engine.context_to_device(
+        eng, state["d"].to_host(), agents, depth, lookback, max_payload=1024)
+    want = want.to_host()
+    assert (want.counts == depth).all(), "a row lacks its history"
+    for name in ("counts", "seqs", "lengths", "headers", "payload"):
+        a, b = getattr(got, name), getattr(want, name)
+        assert np.array_equal(a, b), f"context {name} differs from the double"
+    eng.close()
+    _emit(13, "p2p-gpu-1kb-device-context", n, elapsed,
+          float(np.median(lat) * 1000),
+          {"context": "host" if host_context else "device", "depth": depth,
+           "lookback": lookback, "pairs": pairs})
 
 
 def config3_group_fanout(seconds: float) -> None:
@@ -810,12 +964,14 @@ def config5_loadbalancer(seconds: float) -> None:
 def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", type=int, required=True,
-                    choices=[1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12])
+                    choices=[1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13])
     ap.add_argument("--seconds", type=float, default=5.0)
     ap.add_argument("--host-return", action="store_true",
                     help="config 11: send the replies through the host")
     ap.add_argument("--host-dispatch", action="store_true",
                     help="config 12: dispatch through the host")
+    ap.add_argument("--host-context", action="store_true",
+                    help="config 13: build the context through the host")
     args = ap.parse_args()
     if args.config == 1:
         config1_cpu_loopback(args.seconds)
@@ -852,6 +1008,8 @@ def main() -> int:
         config11_device_echo(args.seconds, args.host_return)
     elif args.config == 12:
         config12_device_dispatch(args.seconds, args.host_dispatch)
+    elif args.config == 13:
+        config13_device_context(args.seconds, args.host_context)
     return 0
 
 

@@ -555,6 +555,257 @@ __global__ void __launch_bounds__(256)
   }
 }
 
+// ---- device-resident conversation context ----
+//
+// For every row r of a delivery: the newest `depth` messages of the log
+// window [lo, hi) that the row's polled agent a and the row's sender s
+// exchanged, in fixed slots (r, j), oldest first. Both kernels only READ
+// queue state and run on stream_, which serialises every mutation of the
+// log: stream order is the only synchronisation.
+//
+// The delivery's seqs / agent_row / headers may have been written to by
+// the consumer, so they are values, never indices: agent_row is range-
+// checked before it picks the polled agent, the sender is compared but
+// never dereferenced, the seq is clamped into [0, count].
+
+// Rows of a delivery one workgroup of k_context_find takes (CONTEXT_GROUP
+// / 4 per wavefront). 4 — one row per wavefront — measured best on a
+// 4096-row tick, where the call is bound by the serial chain of tiles a
+// workgroup walks and not by the log reads the wider group saves; 16 is
+// built too, for the comparison in profiles/device_context.md.
+constexpr int CONTEXT_GROUP = 4;
+constexpr int CONTEXT_GROUP_WIDE = 16;
+constexpr int CONTEXT_TILE = 256;     // seqs per tile: one per thread
+constexpr int CONTEXT_MAX_DEPTH = 64; // one lane per slot
+
+// Step 1: which seqs. The workgroup walks the union window of its G rows
+// from newest to oldest in tiles of 256 seqs. Thread t loads the first
+// 16 B of one record (sender, receiver, type, vis_mode) plus its status
+// word and leaves (sender, receiver, ok | type) in LDS; then every
+// wavefront tests its G/4 rows against the tile, 64 entries per ballot,
+// newest 64 first, each row under its own [lo, hi), and takes matches
+// from the high end of the mask until the row holds `depth`. One
+// 16-B-per-record pass is shared by G rows: where rows of one tick have
+// nearly the same window, the log headers are read ~rows/G times, not
+// rows times. The next tile's loads are issued before the current one is
+// tested. Every branch around a barrier depends on block-uniform values
+// only (top, wlo and the block-wide vote).
+template <int G>
+__global__ void __launch_bounds__(256)
+    k_context_find(const long long *__restrict__ d_seqs,
+                   const int *__restrict__ d_agent_row,
+                   const u32 *__restrict__ d_headers, // 12 words per row
+                   int total, const u32 *__restrict__ agents, int na,
+                   int depth, long long lookback, int type_code,
+                   u64 evict_base, u64 count, const Rec *__restrict__ hdr,
+                   const u32 *__restrict__ status, int *__restrict__ out_counts,
+                   long long *__restrict__ out_seqs,
+                   int *__restrict__ out_lengths, QueueGeom g) {
+  static_assert(G % 4 == 0 && G >= 4, "G/4 rows per wavefront");
+  constexpr int RPW = G / 4;
+  __shared__ u32 t_sender[CONTEXT_TILE];
+  __shared__ u32 t_receiver[CONTEXT_TILE];
+  __shared__ u32 t_ok_type[CONTEXT_TILE]; // bit 8: candidate; bits 0..7: type
+  __shared__ u32 r_a[G], r_s[G];
+  __shared__ long long r_lo[G], r_hi[G]; // lo >= hi: the row takes nothing
+  __shared__ long long found[G][CONTEXT_MAX_DEPTH]; // newest first
+
+  const int tid = (int)threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = tid >> 6;
+  const long long row0 = (long long)blockIdx.x * G;
+
+  if (tid < G) {
+    const long long r = row0 + tid;
+    long long lo = 0, hi = 0;
+    u32 a = 0, s = 0;
+    if (r < total) {
+      const int b = d_agent_row[r];
+      s = d_headers[r * 12];
+      if (b >= 0 && b < na && s < g.max_agents) {
+        a = agents[b];
+        long long q = d_seqs[r];
+        q = q < 0 ? 0 : q;
+        hi = q > (long long)count ? (long long)count : q;
+        lo = hi - lookback;
+        if (lo < (long long)evict_base)
+          lo = (long long)evict_base;
+      }
+    }
+    r_a[tid] = a;
+    r_s[tid] = s;
+    r_lo[tid] = lo;
+    r_hi[tid] = hi;
+  }
+  __syncthreads();
+
+  // this wavefront's rows, and the block's union window
+  u32 ra[RPW], rs[RPW];
+  long long rlo[RPW], rhi[RPW];
+  int rc[RPW];
+#pragma unroll
+  for (int i = 0; i < RPW; ++i) {
+    ra[i] = r_a[wave * RPW + i];
+    rs[i] = r_s[wave * RPW + i];
+    rlo[i] = r_lo[wave * RPW + i];
+    rhi[i] = r_hi[wave * RPW + i];
+    rc[i] = 0;
+  }
+  long long wlo = 0, whi = 0;
+  for (int i = 0; i < G; ++i) {
+    const long long l = r_lo[i], h = r_hi[i];
+    if (l < h) {
+      wlo = (whi == 0 || l < wlo) ? l : wlo;
+      whi = h > whi ? h : whi;
+    }
+  }
+
+  // Thread tid's entry of the tile that ends at t_top (exclusive): seq
+  // max(t_top - 256, wlo) + tid, as the raw record words and status (the
+  // caller decodes them when it needs them, so the loads stay in
+  // flight). One 64-bit modulo per tile; a loaded thread has tid <
+  // t_top - tlo <= whi - evict_base <= num_slots, so one conditional
+  // step wraps its slot. An entry outside the tile reads as DELETED.
+  auto load_tile = [&](long long t_top, uint4 &v, u32 &st) {
+    v = make_uint4(0u, 0u, 0u, 0u);
+    st = ST_DELETED;
+    if (t_top <= wlo)
+      return;
+    const long long tlo =
+        t_top - CONTEXT_TILE > wlo ? t_top - CONTEXT_TILE : wlo;
+    if (tlo + tid >= t_top)
+      return;
+    u32 slot = (u32)((u64)tlo % g.num_slots) + (u32)tid;
+    if (slot >= g.num_slots)
+      slot -= g.num_slots;
+    v = *reinterpret_cast<const uint4 *>(hdr + slot);
+    st = status[slot];
+  };
+
+  long long top = whi; // exclusive end of the next tile; whi == 0: no window
+  uint4 v;
+  u32 st;
+  load_tile(top, v, st);
+  while (top > wlo) {
+    const long long tlo = top - CONTEXT_TILE > wlo ? top - CONTEXT_TILE : wlo;
+    const u32 type = v.z & 0xFFu;
+    const u32 vis = (v.z >> 16) & 0xFFu;
+    const bool ok = st != ST_DELETED && st != ST_FAILED && vis == VIS_ALL &&
+                    (type_code < 0 || type == (u32)type_code);
+    t_sender[tid] = v.x;
+    t_receiver[tid] = v.y;
+    t_ok_type[tid] = (ok ? 0x100u : 0u) | type;
+    __syncthreads();
+    // the next (older) tile's loads fly while this one is tested
+    load_tile(tlo, v, st);
+
+    int open = 0; // a row of this wavefront may still take older seqs
+#pragma unroll
+    for (int i = 0; i < RPW; ++i) {
+      if (rc[i] < depth && rlo[i] < rhi[i] && rhi[i] > tlo && rlo[i] < top) {
+        for (int c = CONTEXT_TILE / 64 - 1; c >= 0 && rc[i] < depth; --c) {
+          const int e = c * 64 + lane;
+          const long long qe = tlo + e;
+          const u32 es = t_sender[e], er = t_receiver[e];
+          const bool m = (t_ok_type[e] & 0x100u) && qe >= rlo[i] &&
+                         qe < rhi[i] && qe < top &&
+                         ((es == rs[i] && er == ra[i]) ||
+                          (es == ra[i] && er == rs[i]));
+          const ull mask = __ballot(m);
+          if (mask) {
+            // matches above this lane come first (newest first)
+            const int above =
+                lane == 63 ? 0 : __popcll(mask >> (lane + 1));
+            const int need = depth - rc[i];
+            if (m && above < need)
+              found[wave * RPW + i][rc[i] + above] = qe;
+            const int got = __popcll(mask);
+            rc[i] += got < need ? got : need;
+          }
+        }
+      }
+      if (rc[i] < depth && rlo[i] < rhi[i] && rlo[i] < tlo)
+        open = 1;
+    }
+    top = tlo;
+    // also the barrier that lets the next tile overwrite the LDS tile
+    if (!__syncthreads_or(open))
+      break;
+  }
+  __syncthreads(); // found[] of the last tile, for the lanes that write out
+
+#pragma unroll
+  for (int i = 0; i < RPW; ++i) {
+    const long long r = row0 + wave * RPW + i;
+    if (r >= total)
+      continue;
+    const int c = rc[i];
+    if (lane < depth) {
+      const long long o = r * depth + lane;
+      if (lane < c) {
+        out_seqs[o] = found[wave * RPW + i][c - 1 - lane]; // chronological
+      } else {
+        out_seqs[o] = -1;
+        out_lengths[o] = 0;
+      }
+    }
+    if (lane == 0)
+      out_counts[r] = c;
+  }
+}
+
+// Step 2: one wavefront per (r, j) slot with a seq, as k_deliver_device
+// copies a row: 16-B lanes, the last chunk masked at payload_len, zero
+// tail to `stride`, the record with payload_off rebased to the slot.
+// k_context_find only hands out seqs of [evict_base, count), so the
+// slot holds the message that seq names.
+__global__ void __launch_bounds__(256)
+    k_context_gather(const long long *__restrict__ ctx_seqs, long long n_slots,
+                     const Rec *__restrict__ hdr,
+                     const u8 *__restrict__ payload, u8 *__restrict__ out_pay,
+                     uint4 *__restrict__ out_hdr, int *__restrict__ out_len,
+                     u32 stride, QueueGeom g) {
+  const long long o = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const u32 lane = threadIdx.x & 63;
+  if (o >= n_slots)
+    return;
+  const long long seq = ctx_seqs[o];
+  if (seq < 0)
+    return;
+  const Rec h = hdr[(u64)seq % g.num_slots];
+  const u32 plen = h.payload_len < stride ? h.payload_len : stride;
+  const u32 full = plen >> 4;
+  const u32 rem = plen & 15u;
+  const u32 row_chunks = stride >> 4;
+  const uint4 *src = reinterpret_cast<const uint4 *>(payload + h.payload_off);
+  uint4 *dst = reinterpret_cast<uint4 *>(out_pay + (u64)o * stride);
+  for (u32 c = lane; c < row_chunks; c += 64) {
+    uint4 v = make_uint4(0u, 0u, 0u, 0u);
+    if (c < full) {
+      v = src[c];
+    } else if (c == full && rem) {
+      v = src[c];
+      v.x &= tail_mask(rem, 0);
+      v.y &= tail_mask(rem, 4);
+      v.z &= tail_mask(rem, 8);
+      v.w &= tail_mask(rem, 12);
+    }
+    dst[c] = v;
+  }
+  if (lane == 0) {
+    Rec hh = h;
+    hh.payload_off = (u64)o * stride;
+    uint4 hv[3];
+    __builtin_memcpy(hv, &hh, sizeof(Rec));
+    uint4 *oh = out_hdr + o * 3;
+    oh[0] = hv[0];
+    oh[1] = hv[1];
+    oh[2] = hv[2];
+  } else if (lane == 1) {
+    out_len[o] = (int)plen;
+  }
+}
+
 // Gather message contents for the host (receive payload delivery, fetch,
 // history spill): one wave per message, dense slot_bytes-strided output.
 __global__ void k_gather(const u64 *__restrict__ seqs, int n,
@@ -2193,6 +2444,82 @@ public:
     HIP_CHECK(hipStreamSynchronize(stream_));
   }
 
+  // Conversation context of the first `total` rows of a device-resident
+  // delivery (k_context_find has the rules), left in the caller's device
+  // buffers: counts int32 [>= total], seqs int64 / lengths int32
+  // [>= total, depth], headers [>= total, depth, 48] and payload
+  // [>= total, depth, stride]. The polled agents are the only H2D and
+  // nothing comes back. `type_code` < 0 means no filter; `group` picks
+  // the rows per workgroup (0: CONTEXT_GROUP). The window bounds are the
+  // host-tracked count_ / evict_base_ every kernel of stream_ is launched
+  // with. Reads queue state only; every check runs before anything is
+  // launched; synchronizes.
+  void context_to_device(uintptr_t seqs_ptr, uintptr_t agent_row_ptr,
+                         uintptr_t headers_ptr, long long total,
+                         py::array_t<u32> agents, int depth,
+                         long long lookback, int type_code, u32 stride,
+                         uintptr_t counts_ptr, uintptr_t ctx_seqs_ptr,
+                         uintptr_t ctx_lengths_ptr, uintptr_t ctx_headers_ptr,
+                         uintptr_t ctx_payload_ptr, int group) {
+    const int na = (int)agents.size();
+    if (total < 0 || total > (1ll << 30) / CONTEXT_MAX_DEPTH)
+      throw std::invalid_argument("context rows out of range");
+    if (depth < 1 || depth > CONTEXT_MAX_DEPTH)
+      throw std::invalid_argument("depth must be within 1..64");
+    if (lookback < 1 || lookback > (long long)INT32_MAX)
+      throw std::invalid_argument("lookback must be within 1..2^31-1");
+    if (type_code > 255)
+      throw std::invalid_argument("type is one byte");
+    if ((u32)na > g_.max_agents)
+      throw std::invalid_argument("more polled agents than max_agents");
+    if (stride < 16 || stride > g_.slot_bytes || stride % 16 != 0)
+      throw std::invalid_argument(
+          "stride must be a multiple of 16 in 16..slot_bytes");
+    if (group == 0)
+      group = CONTEXT_GROUP;
+    if (group != CONTEXT_GROUP && group != CONTEXT_GROUP_WIDE)
+      throw std::invalid_argument("group must be 0, 4 or 16");
+    if (total == 0)
+      return;
+    if (!seqs_ptr || !agent_row_ptr || !headers_ptr || !counts_ptr ||
+        !ctx_seqs_ptr || !ctx_lengths_ptr || !ctx_headers_ptr ||
+        !ctx_payload_ptr)
+      throw std::invalid_argument("context buffer pointer is null");
+    if (seqs_ptr % 8 || agent_row_ptr % 4 || headers_ptr % 16 ||
+        counts_ptr % 4 || ctx_seqs_ptr % 8 || ctx_lengths_ptr % 4 ||
+        ctx_headers_ptr % 16 || ctx_payload_ptr % 16)
+      throw std::invalid_argument("context buffer is misaligned");
+    py::gil_scoped_release nogil;
+    if (na)
+      HIP_CHECK(hipMemcpyAsync(d_agents_, agents.data(), na * sizeof(u32),
+                               hipMemcpyHostToDevice, stream_));
+    const long long n_slots = total * depth;
+#define SWARMQ_CONTEXT_FIND(G)                                                 \
+  hipLaunchKernelGGL(k_context_find<G>,                                        \
+                     dim3((unsigned)((total + (G) - 1) / (G))), dim3(256), 0,  \
+                     stream_, reinterpret_cast<const long long *>(seqs_ptr),   \
+                     reinterpret_cast<const int *>(agent_row_ptr),             \
+                     reinterpret_cast<const u32 *>(headers_ptr), (int)total,   \
+                     d_agents_, na, depth, lookback, type_code, evict_base_,   \
+                     count_, d_hdr_, d_status_,                                \
+                     reinterpret_cast<int *>(counts_ptr),                      \
+                     reinterpret_cast<long long *>(ctx_seqs_ptr),              \
+                     reinterpret_cast<int *>(ctx_lengths_ptr), g_)
+    if (group == CONTEXT_GROUP_WIDE)
+      SWARMQ_CONTEXT_FIND(CONTEXT_GROUP_WIDE);
+    else
+      SWARMQ_CONTEXT_FIND(CONTEXT_GROUP);
+#undef SWARMQ_CONTEXT_FIND
+    hipLaunchKernelGGL(k_context_gather, dim3((unsigned)((n_slots + 3) / 4)),
+                       dim3(256), 0, stream_,
+                       reinterpret_cast<const long long *>(ctx_seqs_ptr),
+                       n_slots, d_hdr_, d_payload_,
+                       reinterpret_cast<u8 *>(ctx_payload_ptr),
+                       reinterpret_cast<uint4 *>(ctx_headers_ptr),
+                       reinterpret_cast<int *>(ctx_lengths_ptr), stride, g_);
+    HIP_CHECK(hipStreamSynchronize(stream_));
+  }
+
   // ---- message store ----
 
   // Returns (hdr bytes [n*48], status[n], payload bytes [n*slot_bytes]).
@@ -3194,6 +3521,8 @@ private:
 PYBIND11_MODULE(_swarmq, m) {
   m.doc() = "MI355X-native GPU message-queue engine (CDNA4 HIP kernels)";
   m.attr("RECV_WINDOW") = RECV_WINDOW;
+  m.attr("CONTEXT_GROUP") = CONTEXT_GROUP;
+  m.attr("CONTEXT_GROUP_WIDE") = CONTEXT_GROUP_WIDE;
 
   m.def("device_count", []() {
     int n = 0;
@@ -3245,6 +3574,13 @@ PYBIND11_MODULE(_swarmq, m) {
            py::arg("capacity_rows"))
       .def("ack_device", &DeviceQueue::ack_device, py::arg("seqs_ptr"),
            py::arg("n"), py::arg("status"))
+      .def("context_to_device", &DeviceQueue::context_to_device,
+           py::arg("seqs_ptr"), py::arg("agent_row_ptr"),
+           py::arg("headers_ptr"), py::arg("total"), py::arg("agents"),
+           py::arg("depth"), py::arg("lookback"), py::arg("type_code"),
+           py::arg("stride"), py::arg("counts_ptr"), py::arg("ctx_seqs_ptr"),
+           py::arg("ctx_lengths_ptr"), py::arg("ctx_headers_ptr"),
+           py::arg("ctx_payload_ptr"), py::arg("group") = 0)
       .def("fetch", &DeviceQueue::fetch)
       .def("fetch_raw", &DeviceQueue::fetch_raw, py::arg("seqs"),
            py::arg("stride") = 0, py::arg("synchronize") = true)

@@ -12,7 +12,7 @@ persistence.
 
 from .core.config import QueueConfig
 from .core.message import Message, MessagePriority, MessageStatus, MessageType
-from .runtime.engine import DeviceDelivery, DeviceDispatch
+from .runtime.engine import DeviceContext, DeviceDelivery, DeviceDispatch
 from .runtime.facade import SwarmsDB
 
 __version__ = "0.2.0"
@@ -26,4 +26,5 @@ __all__ = [
     "MessageStatus",
     "DeviceDelivery",
     "DeviceDispatch",
+    "DeviceContext",
 ]

@@ -339,6 +339,18 @@ class CpuEngine(Engine):
                 )
             )
 
+    def _context_window(self, lo, hi):
+        # the log is dense on the CPU: views, no gather
+        return self._hdr[lo:hi], self._status[lo:hi]
+
+    def context_to_device(self, delivery, agent_idxs, depth, lookback,
+                          type_code=None, max_payload=0, out=None):
+        with self._lock:
+            return super().context_to_device(
+                delivery, agent_idxs, depth, lookback, type_code,
+                max_payload, out,
+            )
+
     def peek_inbox(self, agent_idx: int) -> np.ndarray:
         with self._lock:
             ring = self._inbox.get(agent_idx)

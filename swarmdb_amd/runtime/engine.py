@@ -273,6 +273,119 @@ def check_dispatch_out(out: "DeviceDispatch", n_backends: int, total: int) -> No
             )
 
 
+@dataclass
+class DeviceContext:
+    """The conversation context of every row of a :class:`DeviceDelivery`
+    (:meth:`Engine.context_to_device`): for row ``r``, the newest
+    ``depth`` messages exchanged between the polled agent and the row's
+    sender, oldest first. Slots are fixed — row ``r``, slot ``j`` — so
+    there is no prefix sum and no count to read back. On the GPU engine
+    every array is a ``torch.Tensor`` in HBM on the queue's device; on the
+    CPU engine they are numpy arrays with the same dtypes and layout.
+
+    - ``counts``   int32 [rows]        defined slots of the row
+    - ``seqs``     int64 [rows, D]     ascending; ``-1`` from ``counts[r]`` on
+    - ``lengths``  int32 [rows, D]     ``min(payload_len, stride)``; ``0``
+      in undefined slots
+    - ``headers``  uint8 [rows, D, 48] REC_DTYPE records, ``payload_off``
+      rebased to ``(r * D + j) * stride`` (into ``payload``, flattened)
+    - ``payload``  uint8 [rows, D, stride], zero from ``lengths[r, j]`` on
+
+    ``headers`` and ``payload`` of undefined slots, and everything at rows
+    ``>= total``, are unspecified.
+    """
+
+    counts: Any
+    seqs: Any
+    lengths: Any
+    headers: Any
+    payload: Any
+    depth: int
+    stride: int
+    total: int
+
+    def to_host(self) -> "DeviceContext":
+        """Copy with numpy arrays, trimmed to ``total`` rows; ``headers``
+        comes back as a REC_DTYPE array ``[total, D]``."""
+        t = self.total
+        headers = np.ascontiguousarray(_to_numpy(self.headers[:t]))
+        if headers.dtype != REC_DTYPE:
+            headers = headers.view(REC_DTYPE)
+        return DeviceContext(
+            counts=_to_numpy(self.counts[:t]),
+            seqs=_to_numpy(self.seqs[:t]),
+            lengths=_to_numpy(self.lengths[:t]),
+            headers=headers.reshape(t, self.depth),
+            payload=_to_numpy(self.payload[:t]),
+            depth=self.depth,
+            stride=self.stride,
+            total=t,
+        )
+
+
+MAX_CONTEXT_DEPTH = 64  # one wavefront lane per context slot
+
+
+def check_context_args(
+    depth: int,
+    lookback: int,
+    type_code: Optional[int],
+    agent_idxs: Any,
+    n_polled: int,
+    max_agents: int,
+) -> Tuple[int, int, int, np.ndarray]:
+    """(depth, lookback, type code or -1 for 'no filter', polled agents as
+    uint32 [na]) of :meth:`Engine.context_to_device`, or ValueError."""
+    depth, lookback = int(depth), int(lookback)
+    if not 1 <= depth <= MAX_CONTEXT_DEPTH:
+        raise ValueError(f"depth must be within 1..{MAX_CONTEXT_DEPTH}")
+    if not 1 <= lookback <= 2 ** 31 - 1:
+        raise ValueError("lookback must be within 1..2**31-1")
+    code = -1
+    if type_code is not None:
+        code = int(type_code)
+        if not 0 <= code <= 255:
+            raise ValueError("type_code is one byte")
+    raw = np.asarray(agent_idxs)
+    if raw.ndim != 1 or len(raw) != n_polled:
+        raise ValueError("agent_idxs must be the polled list of the delivery")
+    if len(raw) > max_agents:
+        raise ValueError("more polled agents than max_agents")
+    if len(raw) and raw.dtype.kind not in "iu":
+        raise ValueError("agent_idxs must be an integer array")
+    if len(raw) and (raw.min() < 0 or raw.max() > 0xFFFFFFFF):
+        raise ValueError("agent index out of range")
+    return depth, lookback, code, np.ascontiguousarray(raw, dtype=np.uint32)
+
+
+def check_context_out(
+    out: "DeviceContext", depth: int, stride: int, total: int
+) -> None:
+    """Refuse (ValueError) a reused context built for another ``depth`` or
+    ``stride``, or with fewer than ``total`` rows."""
+    if not isinstance(out, DeviceContext):
+        raise ValueError("out must be a DeviceContext")
+    if out.depth != depth or out.stride != stride:
+        raise ValueError(
+            f"out was built for depth {out.depth} and stride {out.stride}, "
+            f"this call needs {depth} and {stride}"
+        )
+    shapes = {
+        "counts": (), "seqs": (depth,), "lengths": (depth,),
+        "headers": (depth, REC_DTYPE.itemsize), "payload": (depth, stride),
+    }
+    for name, tail in shapes.items():
+        a = getattr(out, name)
+        shape = tuple(getattr(a, "shape", ()))
+        if len(shape) != len(tail) + 1 or shape[1:] != tail:
+            want = ", ".join(["rows"] + [str(d) for d in tail])
+            raise ValueError(f"out.{name} must have shape [{want}]")
+        if shape[0] < total:
+            raise ValueError(
+                f"out.{name} holds {shape[0]} rows, this call needs {total}"
+            )
+
+
 def delivery_stride(max_payload: int, slot_bytes: int) -> int:
     """Row stride of a device-resident delivery: ``max_payload`` rounded up
     to 16 B when it tightens the row below ``slot_bytes``."""
@@ -894,6 +1007,167 @@ class Engine(abc.ABC):
             if added[k]:
                 self.backend_add_load(k, -int(added[k]))
         dispatch.released = True
+
+    # --- device-resident conversation context ---
+
+    def _context_window(self, lo: int, hi: int) -> Tuple[np.ndarray, np.ndarray]:
+        """(headers, statuses) of the seqs ``[lo, hi)`` for the context
+        double. Default: through :meth:`fetch_raw_chunks`."""
+        hdrs, _, _ = self.fetch_raw_chunks(np.arange(lo, hi, dtype=np.uint64))
+        return hdrs, np.asarray(hdrs["status"])
+
+    def context_to_device(
+        self,
+        delivery: DeviceDelivery,
+        agent_idxs: np.ndarray,
+        depth: int,
+        lookback: int,
+        type_code: Optional[int] = None,
+        max_payload: int = 0,
+        out: Optional[DeviceContext] = None,
+    ) -> DeviceContext:
+        """Gather the conversation context of every row of ``delivery``
+        (polled with ``agent_idxs``) from the log into engine-resident
+        arrays (see :class:`DeviceContext`). For each row ``r <
+        delivery.total``, independently of the other rows::
+
+            a  = agent_idxs[agent_row[r]]  if 0 <= agent_row[r] < na  else none
+            s  = headers[r].sender
+            hi = min(max(seqs[r], 0), total_messages())   # exclusive
+            lo = max(evict_base(), hi - lookback)
+            if a is none or s >= max_agents:  count[r] = 0
+            else:
+              match(q) := status(q) not in {DELETED, FAILED}
+                      and hdr(q).vis_mode == VIS_ALL
+                      and (   (hdr(q).sender == s and hdr(q).receiver == a)
+                           or (hdr(q).sender == a and hdr(q).receiver == s))
+                      and (type_code is None or hdr(q).type == type_code)
+              M = the `depth` largest q in [lo, hi) with match(q)
+              count[r] = |M|;  slot j holds the j-th smallest q of M
+
+        The row's own message is never part of its context (``hi`` is
+        exclusive). Broadcasts never match (``receiver`` is BROADCAST),
+        and messages with restricted visibility (VIS_BITMAP, VIS_GROUP)
+        never appear: the context does not show a message whose visibility
+        nobody checked. ``delivery.seqs``, ``agent_row`` and ``headers``
+        may have been written to by the consumer and are values: an
+        out-of-range ``agent_row`` or ``sender`` gives ``count == 0``, an
+        out-of-range seq is clamped. ``max_payload`` tightens the slot
+        stride as in :meth:`receive_to_device`. Only queue state is read:
+        no cursor, status, counter or load changes.
+
+        Every refusal (``depth`` outside ``1..64``, ``lookback`` outside
+        ``1..2**31-1``, a ``type_code`` outside one byte, an
+        ``agent_idxs`` of another length than the delivery's or longer
+        than ``max_agents``, unusable delivery arrays, an ``out`` built
+        for another ``depth`` or stride or with too few rows) is a
+        ValueError raised before anything is gathered.
+
+        Default: the CPU double, plain numpy over the log window."""
+        cfg = self.cfg  # type: ignore[attr-defined]
+        total = int(delivery.total)
+        depth, lookback, code, agents = check_context_args(
+            depth, lookback, type_code, agent_idxs, len(delivery.counts),
+            cfg.max_agents,
+        )
+        na = len(agents)
+        stride = delivery_stride(max_payload, cfg.slot_bytes)
+        dseq, arow, hdr = delivery.seqs, delivery.agent_row, delivery.headers
+        for name, a in (("delivery.seqs", dseq), ("delivery.agent_row", arow),
+                        ("delivery.headers", hdr)):
+            if not isinstance(a, np.ndarray) or not a.flags.c_contiguous:
+                raise ValueError(f"{name} must be a contiguous numpy array")
+        if hdr.dtype == np.uint8 and hdr.ndim == 2 \
+                and hdr.shape[1] == REC_DTYPE.itemsize:
+            hdr = hdr.view(REC_DTYPE).reshape(-1)
+        elif not (hdr.dtype == REC_DTYPE and hdr.ndim == 1):
+            raise ValueError(
+                "delivery.headers must be uint8 [rows, 48] or REC_DTYPE [rows]")
+        if dseq.dtype != np.int64 or dseq.ndim != 1:
+            raise ValueError("delivery.seqs must be int64 [rows]")
+        if arow.dtype != np.int32 or arow.ndim != 1:
+            raise ValueError("delivery.agent_row must be int32 [rows]")
+        if len(hdr) < total or len(arow) < total or len(dseq) < total:
+            raise ValueError("delivery arrays hold fewer rows than its total")
+        D = depth
+        if out is not None:
+            check_context_out(out, D, stride, total)
+            for name in ("counts", "seqs", "lengths", "headers", "payload"):
+                if not isinstance(getattr(out, name), np.ndarray):
+                    raise ValueError(f"out.{name} must be a numpy array")
+            counts, seqs, lengths = out.counts, out.seqs, out.lengths
+            headers, payload = out.headers, out.payload
+        else:
+            rows = len(arow)
+            counts = np.zeros(rows, dtype=np.int32)
+            seqs = np.full((rows, D), -1, dtype=np.int64)
+            lengths = np.zeros((rows, D), dtype=np.int32)
+            headers = np.zeros((rows, D, REC_DTYPE.itemsize), dtype=np.uint8)
+            payload = np.zeros((rows, D, stride), dtype=np.uint8)
+        result = DeviceContext(
+            counts=counts, seqs=seqs, lengths=lengths, headers=headers,
+            payload=payload, depth=D, stride=stride, total=total,
+        )
+        if total == 0:
+            return result
+
+        count, base = int(self.total_messages()), int(self.evict_base())
+        hi = np.clip(dseq[:total], 0, count)
+        lo = np.maximum(base, hi - lookback)
+        ar = arow[:total].astype(np.int64)
+        known = (ar >= 0) & (ar < na)
+        a_of = np.full(total, -1, dtype=np.int64)
+        a_of[known] = agents[ar[known]]
+        s_of = hdr["sender"][:total].astype(np.int64)
+        live = known & (s_of < cfg.max_agents) & (lo < hi)
+
+        counts[:total] = 0
+        seqs[:total] = -1
+        lengths[:total] = 0
+        if live.any():
+            # one pass over the union window; the matches of each
+            # (agent, sender) pair, ascending, serve all its rows
+            wlo, whi = int(lo[live].min()), int(hi[live].max())
+            wh, wst = self._context_window(wlo, whi)
+            ok = (wst != ST_DELETED) & (wst != ST_FAILED) \
+                & (wh["vis_mode"] == VIS_ALL)
+            if code >= 0:
+                ok &= wh["type"] == code
+            snd = wh["sender"].astype(np.int64)
+            rcv = wh["receiver"].astype(np.int64)
+            matches: Dict[Tuple[int, int], np.ndarray] = {}
+            for r in np.flatnonzero(live).tolist():
+                a, s = int(a_of[r]), int(s_of[r])
+                m = matches.get((a, s))
+                if m is None:
+                    pair = ((snd == s) & (rcv == a)) | ((snd == a) & (rcv == s))
+                    m = matches[(a, s)] = np.flatnonzero(ok & pair) + wlo
+                i0 = int(np.searchsorted(m, lo[r]))
+                i1 = int(np.searchsorted(m, hi[r]))
+                took = m[max(i0, i1 - D):i1]
+                counts[r] = len(took)
+                seqs[r, :len(took)] = took
+        rr, jj = np.nonzero(seqs[:total] >= 0)
+        if len(rr):
+            q = seqs[:total][rr, jj].astype(np.uint64)
+            hdrs, flat, fstride = self.fetch_raw_chunks(q)
+            n = len(q)
+            flat = flat.reshape(n, fstride)
+            lens = np.minimum(hdrs["payload_len"], stride).astype(np.int32)
+            w = min(stride, fstride)
+            rows_p = np.zeros((n, stride), dtype=np.uint8)
+            rows_p[:, :w] = flat[:, :w]
+            rows_p[np.arange(stride, dtype=np.int32)[None, :] >= lens[:, None]] = 0
+            recs = np.zeros(n, dtype=REC_DTYPE)
+            for name in REC_DTYPE.names:
+                recs[name] = hdrs[name]
+            recs["payload_off"] = (rr * D + jj).astype(np.uint64) \
+                * np.uint64(stride)
+            payload[rr, jj] = rows_p
+            headers[rr, jj] = recs.view(np.uint8).reshape(
+                n, REC_DTYPE.itemsize)
+            lengths[rr, jj] = lens
+        return result
 
     # --- lifecycle ---
 

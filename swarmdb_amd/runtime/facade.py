@@ -61,6 +61,7 @@ from .engine import (
     VIS_ALL,
     VIS_BITMAP,
     VIS_GROUP,
+    DeviceContext,
     DeviceDelivery,
     DeviceDispatch,
     Engine,
@@ -781,6 +782,76 @@ class SwarmsDB:
         with tracer.span("complete_device"):
             self.engine.release_dispatch(dispatch)
 
+    def context_device(
+        self,
+        delivery: DeviceDelivery,
+        agent_ids: List[str],
+        depth: int = 8,
+        lookback: int = 65536,
+        message_type: Union[MessageType, str, None] = None,
+        max_payload: int = 0,
+        out: Optional[DeviceContext] = None,
+    ) -> DeviceContext:
+        """The conversation context of every row of a
+        :meth:`receive_device` delivery, gathered without leaving the
+        engine's memory — the batch, device-resident form of
+        :meth:`get_conversation`. Row ``r`` gets the newest ``depth``
+        messages, oldest first, that the polled agent and the row's sender
+        exchanged among the ``lookback`` messages logged before the row's
+        own (see :meth:`Engine.context_to_device` for the rules and
+        :class:`DeviceContext` for the tensors). Broadcasts and messages
+        with restricted visibility never appear; with ``message_type``
+        only messages of that type do. ``agent_ids`` is the list the
+        delivery was polled with; unregistered ids, or a list of another
+        length than the delivery's, raise ValueError. Nothing in the queue
+        changes. ``out`` reuses the buffers of an earlier context."""
+        with self._lock:
+            if len(agent_ids) != len(delivery.counts):
+                raise ValueError(
+                    "agent_ids must be the list the delivery was polled with"
+                )
+            unknown = [a for a in agent_ids if a not in self.registered_agents]
+            if unknown:
+                raise ValueError(f"unregistered agents: {unknown}")
+            idxs = np.array(
+                [self._agent_idx[a] for a in agent_ids], dtype=np.uint32
+            )
+        code = None if message_type is None else _type_code(message_type)
+        with tracer.span("context_device", n=int(delivery.total)):
+            return self.engine.context_to_device(
+                delivery, idxs, depth, lookback, code, max_payload, out
+            )
+
+    def messages_from_context(
+        self, ctx: DeviceContext, row: int
+    ) -> List[Message]:
+        """Decode the context of one delivery row into Message objects,
+        oldest first — the debugging / parity bridge of
+        :meth:`context_device`, as :meth:`messages_from_delivery` is of
+        :meth:`receive_device` (a host copy plus per-message Python work;
+        not a hot path)."""
+        h = ctx.to_host()
+        if not 0 <= int(row) < h.total:
+            raise ValueError("row must be within the context's rows")
+        n = int(h.counts[row])
+        hdr, lens = h.headers[row, :n], h.lengths[row, :n]
+        if (lens < hdr["payload_len"]).any():
+            raise ValueError(
+                "context was truncated by max_payload; it cannot be decoded"
+            )
+        rows = np.zeros(n, dtype=_DELIVERY_ROW_DTYPE)
+        for name in REC_DTYPE.names:
+            rows[name] = hdr[name]
+        rows["seq"] = h.seqs[row, :n].astype(np.uint64)
+        if n:
+            rows["status"] = self.engine.statuses(rows["seq"])
+        return [
+            self._reconstruct(
+                rows[j], h.payload[row, j, : int(lens[j])].tobytes()
+            )
+            for j in range(n)
+        ]
+
     def messages_from_delivery(
         self, delivery: DeviceDelivery
     ) -> List[List[Message]]:
@@ -1001,7 +1072,9 @@ class SwarmsDB:
         """Two half-limit queries concatenated, not interleaved (reference
         swarmdb/ main.py:783-808 — kept). ``sort=True``
         opts into chronological interleaving (the behavior the reference
-        presumably intended)."""
+        presumably intended). A GPU-local consumer that needs the history
+        of every message of a poll tick uses :meth:`context_device`: one
+        call for the whole delivery, gathered into HBM tensors."""
         a_to_b = self.query_messages(
             sender_id=agent1_id, receiver_id=agent2_id, limit=limit // 2
         )

@@ -25,9 +25,12 @@ from .engine import (
     REC_DTYPE,
     ST_DELETED,
     ST_PROCESSED,
+    DeviceContext,
     DeviceDelivery,
     DeviceDispatch,
     Engine,
+    check_context_args,
+    check_context_out,
     check_delivery_out,
     check_dispatch_args,
     check_dispatch_out,
@@ -829,6 +832,87 @@ class GpuEngine(Engine):
         with self._lock:
             self.q.release_dispatch(dispatch.added.data_ptr(), nb)
         dispatch.released = True
+
+    # --- device-resident conversation context ---
+
+    def context_to_device(
+        self,
+        delivery: DeviceDelivery,
+        agent_idxs: np.ndarray,
+        depth: int,
+        lookback: int,
+        type_code: Optional[int] = None,
+        max_payload: int = 0,
+        out: Optional[DeviceContext] = None,
+        group: int = 0,
+    ) -> DeviceContext:
+        """k_context_find + k_context_gather over the delivery's own
+        tensors and the HBM-resident log (see
+        :meth:`Engine.context_to_device`): the result stays in torch
+        tensors on the queue's GPU, only the polled agents go to the
+        device and no byte comes back. ``group`` picks the delivery rows
+        one workgroup shares a log pass among (0: the built default,
+        ``_swarmq.CONTEXT_GROUP``, one row per wavefront; 16: four, for
+        measurement). The caller's current torch stream is drained first
+        (the delivery's tensors may still be being written) and the
+        engine's stream is synchronized before return."""
+        torch, dev = self._torch_device()
+        total = int(delivery.total)
+        depth, lookback, code, agents = check_context_args(
+            depth, lookback, type_code, agent_idxs, len(delivery.counts),
+            self.cfg.max_agents,
+        )
+        stride = delivery_stride(max_payload, self._slot_bytes)
+        self._check_device_tensor(
+            "delivery.seqs", delivery.seqs, torch.int64, 1, 8)
+        self._check_device_tensor(
+            "delivery.agent_row", delivery.agent_row, torch.int32, 1, 4)
+        self._check_device_tensor(
+            "delivery.headers", delivery.headers, torch.uint8, 2, 16)
+        if (delivery.headers.shape[0] < total
+                or delivery.headers.shape[1] != REC_DTYPE.itemsize
+                or delivery.agent_row.shape[0] < total
+                or delivery.seqs.shape[0] < total):
+            raise ValueError("delivery tensors hold fewer rows than its total")
+        ext = _load_ext()
+        if group not in (0, ext.CONTEXT_GROUP, ext.CONTEXT_GROUP_WIDE):
+            raise ValueError("group must be 0, 4 or 16")
+        D = depth
+        if out is not None:
+            check_context_out(out, D, stride, total)
+            self._check_device_tensor("out.counts", out.counts, torch.int32, 1, 4)
+            self._check_device_tensor("out.seqs", out.seqs, torch.int64, 2, 8)
+            self._check_device_tensor(
+                "out.lengths", out.lengths, torch.int32, 2, 4)
+            self._check_device_tensor(
+                "out.headers", out.headers, torch.uint8, 3, 16)
+            self._check_device_tensor(
+                "out.payload", out.payload, torch.uint8, 3, 16)
+            counts, seqs, lengths = out.counts, out.seqs, out.lengths
+            headers, payload = out.headers, out.payload
+        else:
+            rows = int(delivery.agent_row.shape[0])
+            counts = torch.empty(rows, dtype=torch.int32, device=dev)
+            seqs = torch.empty((rows, D), dtype=torch.int64, device=dev)
+            lengths = torch.empty((rows, D), dtype=torch.int32, device=dev)
+            headers = torch.empty(
+                (rows, D, REC_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+            payload = torch.empty(
+                (rows, D, stride), dtype=torch.uint8, device=dev)
+        if total:
+            torch.cuda.current_stream(dev).synchronize()
+            with self._lock:
+                self.q.context_to_device(
+                    delivery.seqs.data_ptr(), delivery.agent_row.data_ptr(),
+                    delivery.headers.data_ptr(), total, agents, D, lookback,
+                    code, stride, counts.data_ptr(), seqs.data_ptr(),
+                    lengths.data_ptr(), headers.data_ptr(),
+                    payload.data_ptr(), int(group),
+                )
+        return DeviceContext(
+            counts=counts, seqs=seqs, lengths=lengths, headers=headers,
+            payload=payload, depth=D, stride=stride, total=total,
+        )
 
     # --- lifecycle ---
 
