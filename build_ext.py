@@ -17,7 +17,7 @@ from pathlib import Path
 
 REPO = Path(__file__).resolve().parent
 SRC = [REPO / "csrc" / "swarmq_module.hip"]
-HDRS = [REPO / "csrc" / "swarmq_common.h"]
+HDRS = sorted((REPO / "csrc").glob("*.h"))  # the one source includes them all
 EXT_SUFFIX = sysconfig.get_config_var("EXT_SUFFIX") or ".so"
 OUT = REPO / "swarmdb_amd" / f"_swarmq{EXT_SUFFIX}"
 

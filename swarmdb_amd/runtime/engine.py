@@ -560,6 +560,28 @@ class Engine(abc.ABC):
         )
         return counts, seqs
 
+    def _packed_rows(
+        self, seqs: np.ndarray, stride: int, slots: np.ndarray
+    ) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """Packed rows of ``seqs`` for the numpy doubles, from
+        :meth:`fetch_raw_chunks`: the payload rows (uint8 ``[n, stride]``,
+        zero at and past each row's length), the REC_DTYPE records with
+        ``payload_off`` rebased to ``slots * stride``, and the lengths
+        (``payload_len`` clamped to the stride)."""
+        n = len(seqs)
+        hdrs, flat, fstride = self.fetch_raw_chunks(seqs)
+        flat = flat.reshape(n, fstride)
+        lens = np.minimum(hdrs["payload_len"], stride).astype(np.int32)
+        w = min(stride, fstride)
+        rows = np.zeros((n, stride), dtype=np.uint8)
+        rows[:, :w] = flat[:, :w]
+        rows[np.arange(stride, dtype=np.int32)[None, :] >= lens[:, None]] = 0
+        recs = np.zeros(n, dtype=REC_DTYPE)
+        for name in REC_DTYPE.names:
+            recs[name] = hdrs[name]
+        recs["payload_off"] = slots.astype(np.uint64) * np.uint64(stride)
+        return rows, recs, lens
+
     def receive_to_device(
         self,
         agent_idxs: np.ndarray,
@@ -603,19 +625,8 @@ class Engine(abc.ABC):
         offsets[0] = 0
         offsets[1:] = np.cumsum(counts)
         if total:
-            hdrs, flat, fstride = self.fetch_raw_chunks(seqs)
-            flat = flat.reshape(total, fstride)
-            lens = np.minimum(hdrs["payload_len"], stride).astype(np.int32)
-            w = min(stride, fstride)
-            payload[:total, :w] = flat[:, :w]
-            payload[:total, w:] = 0
-            dead = np.arange(stride, dtype=np.int32)[None, :] >= lens[:, None]
-            payload[:total][dead] = 0
-            recs = np.zeros(total, dtype=REC_DTYPE)
-            for name in REC_DTYPE.names:
-                recs[name] = hdrs[name]
-            recs["payload_off"] = np.arange(total, dtype=np.uint64) * np.uint64(
-                stride
+            payload[:total], recs, lens = self._packed_rows(
+                seqs, stride, np.arange(total)
             )
             headers[:total] = recs.view(np.uint8).reshape(
                 total, REC_DTYPE.itemsize
@@ -1150,23 +1161,10 @@ class Engine(abc.ABC):
         rr, jj = np.nonzero(seqs[:total] >= 0)
         if len(rr):
             q = seqs[:total][rr, jj].astype(np.uint64)
-            hdrs, flat, fstride = self.fetch_raw_chunks(q)
-            n = len(q)
-            flat = flat.reshape(n, fstride)
-            lens = np.minimum(hdrs["payload_len"], stride).astype(np.int32)
-            w = min(stride, fstride)
-            rows_p = np.zeros((n, stride), dtype=np.uint8)
-            rows_p[:, :w] = flat[:, :w]
-            rows_p[np.arange(stride, dtype=np.int32)[None, :] >= lens[:, None]] = 0
-            recs = np.zeros(n, dtype=REC_DTYPE)
-            for name in REC_DTYPE.names:
-                recs[name] = hdrs[name]
-            recs["payload_off"] = (rr * D + jj).astype(np.uint64) \
-                * np.uint64(stride)
-            payload[rr, jj] = rows_p
+            payload[rr, jj], recs, lengths[rr, jj] = self._packed_rows(
+                q, stride, rr * D + jj)
             headers[rr, jj] = recs.view(np.uint8).reshape(
-                n, REC_DTYPE.itemsize)
-            lengths[rr, jj] = lens
+                len(q), REC_DTYPE.itemsize)
         return result
 
     # --- lifecycle ---

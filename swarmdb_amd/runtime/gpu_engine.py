@@ -1,7 +1,7 @@
 """GPU delivery engine — HBM-resident rings via the _swarmq HIP extension.
 
 Implements the :class:`Engine` contract over ``DeviceQueue``
-(csrc/swarmq_module.hip): the message log, inbox rings, read cursors,
+(csrc/swarmq_device_queue.h): the message log, inbox rings, read cursors,
 status words, visibility bitmaps and load counters all live in MI355X
 HBM3E; every hot operation is one H2D staging copy + one CDNA4 kernel.
 
@@ -255,17 +255,18 @@ class GpuEngine(Engine):
     def _torch_device(self):
         """(torch, device) of the queue's GPU for the device-resident
         delivery path; a clear error when torch cannot see the GPU."""
-        import torch
-
         if self._torch_dev is None:
+            import torch
+
             if not torch.cuda.is_available():
                 raise RuntimeError(
                     "torch sees no HIP device: import torch before "
                     "constructing GpuEngine, so that torch's HIP runtime "
                     "initialises first"
                 )
-            self._torch_dev = torch.device("cuda", self.cfg.device_index)
-        return torch, self._torch_dev
+            self._torch_dev = (
+                torch, torch.device("cuda", self.cfg.device_index))
+        return self._torch_dev
 
     def receive_to_device(
         self,
@@ -297,6 +298,8 @@ class GpuEngine(Engine):
             raise ValueError("receive batch exceeds output pool")
         if out is not None:
             check_delivery_out(out, na, rows, stride)
+            # placement only, not _check_device_tensor: its dtype, rank and
+            # alignment tests cost 2-4 us on every tick that reuses `out`
             for name in ("offsets", "seqs", "lengths", "agent_row",
                          "headers", "payload"):
                 t = getattr(out, name)
@@ -376,6 +379,25 @@ class GpuEngine(Engine):
         if t.data_ptr() % align:
             raise ValueError(f"{name} must be {align}-byte aligned")
 
+    def _check_delivery_tensors(self, delivery: DeviceDelivery, total: int,
+                                need_seqs: bool) -> None:
+        """Refuse (ValueError) a delivery whose ``headers`` and
+        ``agent_row`` (and ``seqs``, for a call that reads them) are not
+        device tensors of at least ``total`` rows."""
+        torch, _ = self._torch_device()
+        if need_seqs:
+            self._check_device_tensor(
+                "delivery.seqs", delivery.seqs, torch.int64, 1, 8)
+        self._check_device_tensor(
+            "delivery.headers", delivery.headers, torch.uint8, 2, 16)
+        self._check_device_tensor(
+            "delivery.agent_row", delivery.agent_row, torch.int32, 1, 4)
+        if (delivery.headers.shape[0] < total
+                or delivery.headers.shape[1] != REC_DTYPE.itemsize
+                or delivery.agent_row.shape[0] < total
+                or (need_seqs and delivery.seqs.shape[0] < total)):
+            raise ValueError("delivery tensors hold fewer rows than its total")
+
     def enqueue_from_device(self, headers, payload, n: Optional[int] = None):
         """k_stage_device + the enqueue kernels over torch tensors on the
         queue's GPU (see :meth:`Engine.enqueue_from_device`): no staging
@@ -436,16 +458,9 @@ class GpuEngine(Engine):
             raise ValueError("agent_idxs must be the polled list of the delivery")
         if len(agent_idxs) and int(agent_idxs.max()) >= self.cfg.max_agents:
             raise ValueError("agent index out of range")
-        self._check_device_tensor(
-            "delivery.headers", delivery.headers, torch.uint8, 2, 16)
-        self._check_device_tensor(
-            "delivery.agent_row", delivery.agent_row, torch.int32, 1, 4)
+        self._check_delivery_tensors(delivery, total, need_seqs=False)
         self._check_device_tensor("payload", payload, torch.uint8, 2, 16)
         self._check_device_tensor("lengths", lengths, torch.int32, 1, 4)
-        if (delivery.headers.shape[0] < total
-                or delivery.headers.shape[1] != REC_DTYPE.itemsize
-                or delivery.agent_row.shape[0] < total):
-            raise ValueError("delivery tensors hold fewer rows than its total")
         if payload.shape[0] < total or lengths.shape[0] < total:
             raise ValueError(
                 "payload / lengths hold fewer rows than the delivery")
@@ -776,14 +791,7 @@ class GpuEngine(Engine):
         )
         if na > self.cfg.max_agents:
             raise ValueError("more polled agents than max_agents")
-        self._check_device_tensor(
-            "delivery.headers", delivery.headers, torch.uint8, 2, 16)
-        self._check_device_tensor(
-            "delivery.agent_row", delivery.agent_row, torch.int32, 1, 4)
-        if (delivery.headers.shape[0] < total
-                or delivery.headers.shape[1] != REC_DTYPE.itemsize
-                or delivery.agent_row.shape[0] < total):
-            raise ValueError("delivery tensors hold fewer rows than its total")
+        self._check_delivery_tensors(delivery, total, need_seqs=False)
         if out is not None:
             check_dispatch_out(out, nb, total)
             for name in ("backend", "order", "rank", "offsets"):
@@ -863,17 +871,7 @@ class GpuEngine(Engine):
             self.cfg.max_agents,
         )
         stride = delivery_stride(max_payload, self._slot_bytes)
-        self._check_device_tensor(
-            "delivery.seqs", delivery.seqs, torch.int64, 1, 8)
-        self._check_device_tensor(
-            "delivery.agent_row", delivery.agent_row, torch.int32, 1, 4)
-        self._check_device_tensor(
-            "delivery.headers", delivery.headers, torch.uint8, 2, 16)
-        if (delivery.headers.shape[0] < total
-                or delivery.headers.shape[1] != REC_DTYPE.itemsize
-                or delivery.agent_row.shape[0] < total
-                or delivery.seqs.shape[0] < total):
-            raise ValueError("delivery tensors hold fewer rows than its total")
+        self._check_delivery_tensors(delivery, total, need_seqs=True)
         ext = _load_ext()
         if group not in (0, ext.CONTEXT_GROUP, ext.CONTEXT_GROUP_WIDE):
             raise ValueError("group must be 0, 4 or 16")

@@ -710,6 +710,80 @@ def test_gpu_eviction():
         gpu.close()
 
 
+def fill_batch(senders, receivers, lens, fill, slot=512):
+    """REC_DTYPE records + payload buffer: payload i is lens[i] bytes of
+    `fill`, at offset i * slot of a buffer that holds nothing else."""
+    n = len(senders)
+    recs = np.zeros(n, dtype=REC_DTYPE)
+    recs["sender"] = senders
+    recs["receiver"] = receivers
+    recs["priority"] = 1
+    recs["timestamp"] = 1.7e9
+    recs["vis_mode"] = VIS_ALL
+    recs["bitmap"] = NO_BITMAP
+    recs["payload_off"] = np.arange(n, dtype=np.uint64) * slot
+    recs["payload_len"] = lens
+    recs["content_len"] = lens
+    buf = np.zeros(n * slot + 16, dtype=np.uint8)
+    for i, ln in enumerate(lens):
+        buf[i * slot:i * slot + ln] = fill
+    return recs, buf.tobytes()
+
+
+@pytest.mark.gpu
+def test_gpu_stale_tail_after_ring_wrap():
+    """The twin of the delivery test of this name: every slot of a 64-slot
+    ring first holds 512 bytes of 0xFF and is then reused by a payload of
+    0..33 bytes of 0x41. A context slot shows the new payload, zeros from
+    its length to the stride, and never the previous occupant's bytes —
+    also where the stride (16) cuts a payload short."""
+    import torch  # noqa: F401
+
+    gpu, cpu = gpu_and_twin(num_slots=64, inbox_capacity=256)
+    try:
+        register([gpu, cpu], 2)
+        both = np.array([0, 1], dtype=np.uint32)
+        snd = np.arange(64) % 2  # 0 -> 1, 1 -> 0, ...
+        enqueue([gpu, cpu], *fill_batch(snd, 1 - snd, [512] * 64, 0xFF))
+        for e in (gpu, cpu):
+            assert e.receive_to_device(both, 64).total == 64
+        cyc = [0, 1, 5, 15, 16, 17, 31, 32, 33]
+        lens = [cyc[i % len(cyc)] for i in range(64)]
+        seqs = enqueue([gpu, cpu], *fill_batch(snd, 1 - snd, lens, 0x41))
+        assert seqs.tolist() == list(range(64, 128))  # every slot is reused
+        assert gpu.evict_base() == 64
+        # the twin's log has no ring: what the ring evicted is deleted there
+        for q in range(64):
+            assert cpu.delete(q)
+        agents = np.array([1], dtype=np.uint32)
+        dg = gpu.receive_to_device(agents, 64)
+        dc = cpu.receive_to_device(agents, 64)
+        assert dg.total == dc.total == 32
+        len_of = dict(zip(seqs.tolist(), lens))
+        for max_payload, stride in ((0, 512), (16, 16)):
+            g = gpu.context_to_device(dg, agents, 8, 128,
+                                      max_payload=max_payload)
+            c = cpu.context_to_device(dc, agents, 8, 128,
+                                      max_payload=max_payload)
+            assert g.stride == stride
+            h = g.to_host()
+            live = h.seqs >= 0
+            assert live.sum() == sum(min(8, 2 * r) for r in range(32))
+            assert h.seqs[live].min() == 64
+            plen = np.array([len_of[q] for q in h.seqs[live].tolist()])
+            assert set(plen.tolist()) == set(cyc)
+            np.testing.assert_array_equal(h.headers["payload_len"][live], plen)
+            np.testing.assert_array_equal(
+                h.lengths[live], np.minimum(plen, stride))
+            rows = h.payload[live]
+            below = np.arange(stride)[None, :] < h.lengths[live][:, None]
+            assert (rows[below] == 0x41).all()
+            assert not rows[~below].any()
+            assert_same_context(g, c)
+    finally:
+        gpu.close()
+
+
 @pytest.mark.gpu
 def test_gpu_status_filter_and_tampered_rows():
     """A match deleted and another marked FAILED after the delivery never
