@@ -31,159 +31,38 @@ public:
       throw std::invalid_argument("recv_window must be a power of two >= 64");
     g_.recv_window = recv_window;
 
-    HIP_CHECK(hipSetDevice(device_));
-    HIP_CHECK(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
-    HIP_CHECK(hipStreamCreateWithFlags(&copy_stream_, hipStreamNonBlocking));
-    HIP_CHECK(hipStreamCreateWithFlags(&h2d_stream_, hipStreamNonBlocking));
-    HIP_CHECK(hipStreamCreateWithFlags(&lb_stream_, hipStreamNonBlocking));
-    HIP_CHECK(hipEventCreateWithFlags(&ev_, hipEventDisableTiming));
-    HIP_CHECK(hipEventCreateWithFlags(&up_ev_[0], hipEventDisableTiming));
-    HIP_CHECK(hipEventCreateWithFlags(&up_ev_[1], hipEventDisableTiming));
-    HIP_CHECK(hipEventCreateWithFlags(&d2h_ev_[0], hipEventDisableTiming));
-    HIP_CHECK(hipEventCreateWithFlags(&d2h_ev_[1], hipEventDisableTiming));
-
-    // device state
-    HIP_CHECK(hipMalloc(&d_hdr_, (size_t)num_slots * sizeof(Rec)));
-    HIP_CHECK(hipMalloc(&d_status_, (size_t)num_slots * sizeof(u32)));
-    HIP_CHECK(hipMalloc(&d_payload_, (size_t)num_slots * slot_bytes));
-    HIP_CHECK(
-        hipMalloc(&d_inbox_, (size_t)max_agents * inbox_capacity * sizeof(u64)));
-    HIP_CHECK(hipMalloc(&d_wpos_, (size_t)max_agents * sizeof(ull)));
-    HIP_CHECK(hipMalloc(&d_rpos_, (size_t)max_agents * sizeof(ull)));
-    HIP_CHECK(hipMalloc(&d_carry_,
-                        (size_t)max_agents * g_.recv_window * sizeof(u64)));
-    HIP_CHECK(hipMalloc(&d_carry_n_, (size_t)max_agents * sizeof(u32)));
-    HIP_CHECK(hipMalloc(&d_active_, (size_t)max_agents * sizeof(u32)));
-    HIP_CHECK(hipMalloc(&d_bitmaps_,
-                        (size_t)num_bitmaps * g_.bitmap_words * sizeof(u64)));
-    HIP_CHECK(hipMalloc(&d_bitmap_epochs_, (size_t)num_bitmaps * sizeof(u32)));
-    HIP_CHECK(hipMemset(d_bitmap_epochs_, 0xFF,
-                        (size_t)num_bitmaps * sizeof(u32))); // all EPOCH_NONE
-    HIP_CHECK(hipMalloc(&d_dropped_, sizeof(ull)));
-    HIP_CHECK(hipMemset(d_dropped_, 0, sizeof(ull)));
-    HIP_CHECK(hipMalloc(&d_by_type_, N_TYPES * sizeof(ull)));
-    HIP_CHECK(hipMalloc(&d_by_status_, N_STATUS * sizeof(ull)));
-    HIP_CHECK(hipMalloc(&d_sent_, (size_t)max_agents * sizeof(ull)));
-    HIP_CHECK(hipMalloc(&d_received_, (size_t)max_agents * sizeof(ull)));
-    HIP_CHECK(hipMalloc(&d_bcast_, (size_t)staging_batch * sizeof(u64)));
-    HIP_CHECK(hipMalloc(&d_bcast_count_, sizeof(u32)));
-    HIP_CHECK(hipMalloc(&d_backend_loads_, (size_t)num_backends * sizeof(ull)));
-    HIP_CHECK(hipMalloc(&d_choices_, (size_t)staging_batch * sizeof(u32)));
-    HIP_CHECK(hipMalloc(&d_lb_out_, (size_t)staging_batch * sizeof(u32)));
-    HIP_CHECK(hipMalloc(&d_match_, (size_t)staging_batch * sizeof(u64)));
-    HIP_CHECK(hipMalloc(&d_match_count_, sizeof(u32)));
-    HIP_CHECK(hipMalloc(&d_needle_, 256));
-    HIP_CHECK(hipMalloc(&d_agents_, (size_t)max_agents * sizeof(u32)));
-    HIP_CHECK(hipMalloc(&d_unread_, (size_t)max_agents * sizeof(u32)));
-
-    HIP_CHECK(hipMalloc(&d_dyn_, 2 * sizeof(u64)));
-    HIP_CHECK(hipMalloc(&d_tail_, sizeof(ull)));
-    HIP_CHECK(hipMemset(d_tail_, 0, sizeof(ull)));
-    out_pool_ = (size_t)4 << 20; // receive output pool: 4M entries, 32 MB
-    HIP_CHECK(hipMalloc(&d_out_seqs_, out_pool_ * sizeof(u64)));
-    HIP_CHECK(hipMalloc(&d_out_counts_, (size_t)max_agents * sizeof(u32)));
-
-    // staging (device side of the H2D batch), double-buffered so the
-    // host can fill batch i+1 while batch i's H2D/kernels run
-    stage_pay_bytes_ = (size_t)staging_batch * 1024; // grows on demand
-    for (int s = 0; s < 2; ++s) {
-      HIP_CHECK(hipMalloc(&d_stage_recs_[s], (size_t)staging_batch * sizeof(Rec)));
-      HIP_CHECK(hipMalloc(&d_stage_pay_[s], stage_pay_bytes_));
-      HIP_CHECK(hipEventCreateWithFlags(&stage_ev_[s], hipEventDisableTiming));
+    try {
+      init(num_slots, slot_bytes, max_agents, inbox_capacity, num_bitmaps,
+           num_backends, staging_batch);
+    } catch (...) {
+      release(); // the destructor of a half-built object never runs
+      throw;
     }
-    HIP_CHECK(hipMalloc(&d_seqs_in_, (size_t)staging_batch * sizeof(u64)));
-    HIP_CHECK(hipMalloc(&d_fetch_hdr_, (size_t)staging_batch * sizeof(Rec)));
-    HIP_CHECK(hipMalloc(&d_fetch_status_, (size_t)staging_batch * sizeof(u32)));
-    HIP_CHECK(hipMalloc(&d_fetch_pay_, (size_t)staging_batch * slot_bytes));
-
-    // pinned host staging
-    for (int s = 0; s < 2; ++s) {
-      HIP_CHECK(hipHostMalloc(&h_recs_[s], (size_t)staging_batch * sizeof(Rec)));
-      HIP_CHECK(hipHostMalloc(&h_pay_[s], stage_pay_bytes_));
-    }
-    HIP_CHECK(hipHostMalloc(&h_out_seqs_, out_pool_ * sizeof(u64)));
-    HIP_CHECK(hipHostMalloc(&h_out_counts_, (size_t)max_agents * sizeof(u32)));
-    HIP_CHECK(hipHostMalloc(&h_fetch_hdr_, (size_t)staging_batch * sizeof(Rec)));
-    HIP_CHECK(
-        hipHostMalloc(&h_fetch_status_, (size_t)staging_batch * sizeof(u32)));
-    HIP_CHECK(hipHostMalloc(&h_fetch_pay_, (size_t)staging_batch * slot_bytes));
-    HIP_CHECK(hipHostMalloc(&h_choices_, (size_t)staging_batch * sizeof(u32)));
-
-    // zero all mutable state
-    HIP_CHECK(hipMemset(d_status_, 0, (size_t)num_slots * sizeof(u32)));
-    HIP_CHECK(hipMemset(d_wpos_, 0, (size_t)max_agents * sizeof(ull)));
-    HIP_CHECK(hipMemset(d_rpos_, 0, (size_t)max_agents * sizeof(ull)));
-    HIP_CHECK(hipMemset(d_carry_n_, 0, (size_t)max_agents * sizeof(u32)));
-    HIP_CHECK(hipMemset(d_active_, 0, (size_t)max_agents * sizeof(u32)));
-    HIP_CHECK(hipMemset(d_by_type_, 0, N_TYPES * sizeof(ull)));
-    HIP_CHECK(hipMemset(d_by_status_, 0, N_STATUS * sizeof(ull)));
-    HIP_CHECK(hipMemset(d_sent_, 0, (size_t)max_agents * sizeof(ull)));
-    HIP_CHECK(hipMemset(d_received_, 0, (size_t)max_agents * sizeof(ull)));
-    HIP_CHECK(hipMemset(d_backend_loads_, 0, (size_t)num_backends * sizeof(ull)));
-
-    // device-resident send: sanitised records, and the per-workgroup
-    // reply counts / offsets of the compaction (256 rows per workgroup).
-    // Allocated last, so that every buffer above sits where it did
-    // before these existed (profiles/device_send.md)
-    const size_t reply_blocks = ((size_t)staging_batch + 255) / 256;
-    HIP_CHECK(hipMalloc(&d_dev_recs_, (size_t)staging_batch * sizeof(Rec)));
-    HIP_CHECK(hipMalloc(&d_reply_blk_, reply_blocks * sizeof(u32)));
-    HIP_CHECK(hipMalloc(&d_reply_off_, (reply_blocks + 1) * sizeof(u32)));
-    HIP_CHECK(hipHostMalloc(&h_reply_m_, sizeof(u32)));
-
-    // device-resident dispatch: the device copy of the pins (one word per
-    // polled agent) and the per-backend row counts with their pinned
-    // landing buffer. Last again, for the same reason
-    HIP_CHECK(hipMalloc(&d_disp_pinned_, (size_t)max_agents * sizeof(int)));
-    HIP_CHECK(hipMalloc(&d_disp_counts_, 64 * sizeof(u32)));
-    HIP_CHECK(hipHostMalloc(&h_disp_counts_, 64 * sizeof(u32)));
   }
 
   ~DeviceQueue() { release(); }
 
+  // Idempotent, and tolerant of members that were never created (a
+  // constructor that threw part-way). Every stream may hold work against
+  // a buffer, so all four drain before anything is freed.
   void release() {
     if (released_)
       return;
     released_ = true;
-    (void)hipStreamSynchronize(stream_);
-    (void)hipStreamSynchronize(copy_stream_);
-    for (void *p :
-         std::vector<void *>{d_hdr_, d_status_, d_payload_, d_inbox_, d_wpos_,
-                             d_rpos_, d_carry_, d_carry_n_, d_active_,
-                             d_bitmaps_, d_bitmap_epochs_, d_dropped_,
-                             d_by_type_, d_by_status_, d_sent_,
-                             d_received_, d_bcast_, d_bcast_count_,
-                             d_backend_loads_, d_choices_, d_lb_out_, d_match_,
-                             d_match_count_, d_needle_, d_agents_, d_unread_,
-                             d_dyn_, d_tail_,
-                             d_out_seqs_, d_out_counts_, d_stage_recs_[0],
-                             d_stage_recs_[1], d_stage_pay_[0],
-                             d_stage_pay_[1], d_seqs_in_, d_fetch_hdr_,
-                             d_fetch_status_, d_fetch_pay_, d_dev_recs_,
-                             d_reply_blk_, d_reply_off_, d_disp_pinned_,
-                             d_disp_counts_})
-      (void)hipFree(p);
-    for (void *p : std::vector<void *>{h_recs_[0], h_recs_[1], h_pay_[0],
-                                       h_pay_[1], h_out_seqs_,
-                                       h_out_counts_, h_fetch_hdr_,
-                                       h_fetch_status_, h_fetch_pay_,
-                                       h_choices_, h_reply_m_,
-                                       h_disp_counts_})
-      (void)hipHostFree(p);
-    (void)hipEventDestroy(stage_ev_[0]);
-    (void)hipEventDestroy(stage_ev_[1]);
-    for (int s = 0; s < 2; ++s)
-      if (tick_exec_[s])
-        (void)hipGraphExecDestroy(tick_exec_[s]);
-    (void)hipEventDestroy(ev_);
-    (void)hipEventDestroy(up_ev_[0]);
-    (void)hipEventDestroy(up_ev_[1]);
-    (void)hipEventDestroy(d2h_ev_[0]);
-    (void)hipEventDestroy(d2h_ev_[1]);
-    (void)hipStreamDestroy(stream_);
-    (void)hipStreamDestroy(copy_stream_);
-    (void)hipStreamDestroy(h2d_stream_);
-    (void)hipStreamDestroy(lb_stream_);
+    for (hipStream_t *s : streams())
+      if (*s)
+        (void)hipStreamSynchronize(*s);
+    buf_.free_all();
+    for (hipGraphExec_t &g : tick_exec_)
+      if (g)
+        (void)hipGraphExecDestroy(g);
+    for (hipEvent_t *e : {&stage_ev_[0], &stage_ev_[1], &ev_, &up_ev_[0],
+                          &up_ev_[1], &d2h_ev_[0], &d2h_ev_[1]})
+      if (*e)
+        (void)hipEventDestroy(*e);
+    for (hipStream_t *s : streams())
+      if (*s)
+        (void)hipStreamDestroy(*s);
   }
 
   // ---- registry ----
@@ -212,46 +91,19 @@ public:
   // ---- send plane ----
 
   // recs: n x 48 bytes (REC_DTYPE), payload_off 16-B aligned into `pay`.
-  // Returns base seq. The stream sync at the end is the DELIVERED ack.
+  // Fills and enqueues staging slot 0. Returns base seq. The stream sync
+  // at the end is the DELIVERED ack.
   u64 enqueue_batch(py::buffer recs, py::buffer pay, int n) {
     py::buffer_info ri = recs.request(), pi = pay.request();
     if ((size_t)ri.size * ri.itemsize < (size_t)n * sizeof(Rec))
       throw std::invalid_argument("recs buffer too small");
     if (n <= 0)
       return count_;
-    if ((u32)n > staging_batch_)
-      throw std::invalid_argument("batch exceeds staging_batch");
-    const size_t pay_bytes = (size_t)pi.size * pi.itemsize;
-    ensure_stage_pay(pay_bytes + 16);
-
-    const u64 base = count_;
-    {
-      py::gil_scoped_release nogil;
-      std::memcpy(h_recs_[0], ri.ptr, (size_t)n * sizeof(Rec));
-      if (pay_bytes)
-        par_memcpy(h_pay_[0], pi.ptr, pay_bytes);
-      HIP_CHECK(hipMemcpyAsync(d_stage_recs_[0], h_recs_[0],
-                               (size_t)n * sizeof(Rec),
-                               hipMemcpyHostToDevice, stream_));
-      if (pay_bytes)
-        HIP_CHECK(hipMemcpyAsync(d_stage_pay_[0], h_pay_[0], pay_bytes,
-                                 hipMemcpyHostToDevice, stream_));
-      HIP_CHECK(hipEventRecord(stage_ev_[0], stream_));
-      HIP_CHECK(hipMemsetAsync(d_bcast_count_, 0, sizeof(u32), stream_));
-      launch_enqueue(d_stage_recs_[0], d_stage_pay_[0], n, base);
-      HIP_CHECK(hipStreamSynchronize(stream_));
-    }
-    advance_count(base, (u64)n);
+    check_batch(n);
+    fill_slot(0, ri, pi, n);
+    const u64 base = enqueue_staged(0);
+    sync();
     return base;
-  }
-
-  // Async variant: fill slot 0 and launch without a sync; caller must
-  // sync() (or rely on stream ordering) before reading results.
-  u64 enqueue_batch_async(py::buffer recs, py::buffer pay, int n) {
-    if (n <= 0)
-      return count_;
-    stage_fill(0, recs, pay, n);
-    return enqueue_staged(0);
   }
 
   void sync() {
@@ -263,23 +115,9 @@ public:
   // H2D/kernels are in flight ----
 
   void stage_fill(int slot, py::buffer recs, py::buffer pay, int n) {
-    if (slot < 0 || slot > 1)
-      throw std::invalid_argument("slot must be 0 or 1");
-    if ((u32)n > staging_batch_)
-      throw std::invalid_argument("batch exceeds staging_batch");
-    py::buffer_info ri = recs.request(), pi = pay.request();
-    const size_t pay_bytes = (size_t)pi.size * pi.itemsize;
-    ensure_stage_pay(pay_bytes + 16);
-    {
-      py::gil_scoped_release nogil;
-      // don't overwrite pinned memory a previous H2D still reads
-      HIP_CHECK(hipEventSynchronize(stage_ev_[slot]));
-      std::memcpy(h_recs_[slot], ri.ptr, (size_t)n * sizeof(Rec));
-      if (pay_bytes)
-        par_memcpy(h_pay_[slot], pi.ptr, pay_bytes);
-    }
-    staged_n_[slot] = n;
-    staged_pay_[slot] = pay_bytes;
+    check_slot(slot);
+    check_batch(n);
+    fill_slot(slot, recs.request(), pay.request(), n);
   }
 
   // Allocate pinned host memory exposed as a numpy array (freed by the
@@ -299,78 +137,41 @@ public:
   // (one tick later with double-buffered slots).
   void prefetch_from(int slot, uintptr_t recs_ptr, uintptr_t pay_ptr, int n,
                      size_t pay_bytes) {
-    if (slot < 0 || slot > 1)
-      throw std::invalid_argument("slot must be 0 or 1");
-    if ((u32)n > staging_batch_)
-      throw std::invalid_argument("batch exceeds staging_batch");
+    check_slot(slot);
+    check_batch(n);
     ensure_stage_pay(pay_bytes + 16);
-    {
-      py::gil_scoped_release nogil;
-      HIP_CHECK(hipMemcpyAsync(d_stage_recs_[slot],
-                               reinterpret_cast<void *>(recs_ptr),
-                               (size_t)n * sizeof(Rec),
-                               hipMemcpyHostToDevice, h2d_stream_));
-      if (pay_bytes)
-        HIP_CHECK(hipMemcpyAsync(d_stage_pay_[slot],
-                                 reinterpret_cast<void *>(pay_ptr), pay_bytes,
-                                 hipMemcpyHostToDevice, h2d_stream_));
-      HIP_CHECK(hipEventRecord(stage_ev_[slot], h2d_stream_));
-      HIP_CHECK(hipEventRecord(up_ev_[slot], h2d_stream_));
-    }
     staged_n_[slot] = n;
     staged_pay_[slot] = pay_bytes;
-    uploaded_[slot] = true;
+    py::gil_scoped_release nogil;
+    prefetch_slot(slot, reinterpret_cast<void *>(recs_ptr),
+                  reinterpret_cast<void *>(pay_ptr));
   }
 
   // Upload a filled slot's staging buffers on the dedicated H2D stream
   // (overlaps the main stream's kernels and the copy stream's delivery
   // D2H — PCIe is full duplex). enqueue_staged picks the upload up.
   void prefetch_staged(int slot) {
-    if (slot < 0 || slot > 1)
-      throw std::invalid_argument("slot must be 0 or 1");
-    const int n = staged_n_[slot];
-    if (n <= 0)
+    check_slot(slot);
+    if (staged_n_[slot] <= 0)
       return;
-    const size_t pay_bytes = staged_pay_[slot];
     py::gil_scoped_release nogil;
-    HIP_CHECK(hipMemcpyAsync(d_stage_recs_[slot], h_recs_[slot],
-                             (size_t)n * sizeof(Rec), hipMemcpyHostToDevice,
-                             h2d_stream_));
-    if (pay_bytes)
-      HIP_CHECK(hipMemcpyAsync(d_stage_pay_[slot], h_pay_[slot], pay_bytes,
-                               hipMemcpyHostToDevice, h2d_stream_));
-    HIP_CHECK(hipEventRecord(stage_ev_[slot], h2d_stream_));
-    HIP_CHECK(hipEventRecord(up_ev_[slot], h2d_stream_));
-    uploaded_[slot] = true;
+    prefetch_slot(slot, h_recs_[slot], h_pay_[slot]);
   }
 
   // Launch H2D + enqueue kernels for a previously filled slot; returns
   // the base seq. NO sync — receive_many on the same stream is ordered
   // after it.
   u64 enqueue_staged(int slot) {
-    if (slot < 0 || slot > 1)
-      throw std::invalid_argument("slot must be 0 or 1");
+    check_slot(slot);
     const int n = staged_n_[slot];
     if (n <= 0)
       return count_;
-    const size_t pay_bytes = staged_pay_[slot];
     const u64 base = count_;
     {
       py::gil_scoped_release nogil;
-      if (uploaded_[slot]) {
-        // already uploaded by prefetch_staged: order kernels after it
-        HIP_CHECK(hipStreamWaitEvent(stream_, up_ev_[slot], 0));
-        uploaded_[slot] = false;
-      } else {
-        HIP_CHECK(hipMemcpyAsync(d_stage_recs_[slot], h_recs_[slot],
-                                 (size_t)n * sizeof(Rec),
-                                 hipMemcpyHostToDevice, stream_));
-        if (pay_bytes)
-          HIP_CHECK(hipMemcpyAsync(d_stage_pay_[slot], h_pay_[slot],
-                                   pay_bytes, hipMemcpyHostToDevice, stream_));
-        HIP_CHECK(hipEventRecord(stage_ev_[slot], stream_));
-      }
-      HIP_CHECK(hipMemsetAsync(d_bcast_count_, 0, sizeof(u32), stream_));
+      // already uploaded by a prefetch: order the kernels after it
+      if (!wait_prefetch(slot))
+        upload_slot(slot, h_recs_[slot], h_pay_[slot], stream_);
       launch_enqueue(d_stage_recs_[slot], d_stage_pay_[slot], n, base);
     }
     advance_count(base, (u64)n);
@@ -402,24 +203,13 @@ public:
     for (int s = 0; s < 2; ++s) {
       hipGraph_t graph;
       HIP_CHECK(hipStreamBeginCapture(stream_, hipStreamCaptureModeThreadLocal));
+      // the reset goes ahead of k_tick_begin, where it always was
       HIP_CHECK(hipMemsetAsync(d_bcast_count_, 0, sizeof(u32), stream_));
       hipLaunchKernelGGL(k_tick_begin, dim3(1), dim3(64), 0, stream_, d_dyn_,
                          d_tail_, n, (u64)g_.num_slots);
-      hipLaunchKernelGGL(k_enqueue_meta, dim3((n + 255) / 256), dim3(256), 0,
-                         stream_, d_stage_recs_[s], n, 0, d_dyn_, d_hdr_,
-                         d_status_, d_inbox_, d_wpos_, d_rpos_, d_by_type_,
-                         d_by_status_, d_sent_, d_bcast_, d_bcast_count_,
-                         d_dropped_, g_);
-      hipLaunchKernelGGL(k_enqueue_payload, dim3((n + 3) / 4), dim3(256), 0,
-                         stream_, d_stage_recs_[s], d_stage_pay_[s], n, 0,
-                         d_dyn_, d_payload_, g_);
-      hipLaunchKernelGGL(k_fanout, dim3((g_.max_agents + 255) / 256),
-                         dim3(256), 0, stream_, d_bcast_, d_bcast_count_,
-                         d_active_, d_hdr_, d_bitmaps_, d_bitmap_epochs_,
-                         d_inbox_, d_wpos_, d_rpos_, d_dropped_, g_);
+      launch_enqueue(d_stage_recs_[s], d_stage_pay_[s], n, 0, d_dyn_, false);
       launch_receive(na, K, priority, 0, d_dyn_);
-      HIP_CHECK(hipMemcpyAsync(h_out_counts_, d_out_counts_, na * sizeof(u32),
-                               hipMemcpyDeviceToHost, stream_));
+      counts_to_host(d_out_counts_, na);
       HIP_CHECK(hipMemcpyAsync(h_out_seqs_, d_out_seqs_,
                                (size_t)na * K * sizeof(u64),
                                hipMemcpyDeviceToHost, stream_));
@@ -435,27 +225,18 @@ public:
   // Replay the captured tick for a slot previously uploaded with
   // prefetch_from/prefetch_staged. Returns (counts, seqs).
   py::tuple run_tick(int slot) {
-    if (slot < 0 || slot > 1 || !tick_exec_[slot])
+    if (bad_slot(slot) || !tick_exec_[slot])
       throw std::invalid_argument("tick graph not built for this slot");
     py::array_t<u32> counts(tick_na_);
     py::array_t<u64> seqs((size_t)tick_na_ * tick_K_);
     {
       py::gil_scoped_release nogil;
-      if (uploaded_[slot]) {
-        HIP_CHECK(hipStreamWaitEvent(stream_, up_ev_[slot], 0));
-        uploaded_[slot] = false;
-      }
+      wait_prefetch(slot);
       HIP_CHECK(hipGraphLaunch(tick_exec_[slot], stream_));
       HIP_CHECK(hipStreamSynchronize(stream_));
     }
     advance_count(count_, (u64)tick_n_);
-    last_recv_na_ = tick_na_;
-    last_recv_K_ = tick_K_;
-    std::memcpy(counts.mutable_data(), h_out_counts_,
-                tick_na_ * sizeof(u32));
-    std::memcpy(seqs.mutable_data(), h_out_seqs_,
-                (size_t)tick_na_ * tick_K_ * sizeof(u64));
-    return py::make_tuple(counts, seqs);
+    return received(counts, seqs, tick_na_, tick_K_);
   }
 
   // ---- GPU-direct cross-GPU routing support ----
@@ -505,7 +286,6 @@ public:
     const u64 base = count_;
     {
       py::gil_scoped_release nogil;
-      HIP_CHECK(hipMemsetAsync(d_bcast_count_, 0, sizeof(u32), stream_));
       launch_enqueue(reinterpret_cast<const Rec *>(recs_ptr),
                      reinterpret_cast<const u8 *>(pay_ptr), n, base);
     }
@@ -537,7 +317,6 @@ public:
       hipLaunchKernelGGL(k_stage_device, dim3((n + 255) / 256), dim3(256), 0,
                          stream_, reinterpret_cast<const uint4 *>(headers_ptr),
                          n, stride, g_.num_bitmaps, d_dev_recs_);
-      HIP_CHECK(hipMemsetAsync(d_bcast_count_, 0, sizeof(u32), stream_));
       launch_enqueue(d_dev_recs_, reinterpret_cast<const u8 *>(payload_ptr), n,
                      base);
       HIP_CHECK(hipStreamSynchronize(stream_));
@@ -597,7 +376,6 @@ public:
       if (m > (u32)total) // cannot happen: at most one reply per row
         throw std::runtime_error("reply compaction overran its rows");
       if (m) {
-        HIP_CHECK(hipMemsetAsync(d_bcast_count_, 0, sizeof(u32), stream_));
         launch_enqueue(d_dev_recs_, reinterpret_cast<const u8 *>(payload_ptr),
                        (int)m, base);
         HIP_CHECK(hipStreamSynchronize(stream_));
@@ -666,21 +444,14 @@ public:
       py::gil_scoped_release nogil;
       upload_agents(agents.data(), na);
       launch_receive(na, max_per_agent, priority, evict_base_, nullptr);
-      HIP_CHECK(hipMemcpyAsync(h_out_counts_, d_out_counts_, na * sizeof(u32),
-                               hipMemcpyDeviceToHost, stream_));
+      counts_to_host(d_out_counts_, na);
       if (return_seqs)
         HIP_CHECK(hipMemcpyAsync(h_out_seqs_, d_out_seqs_,
                                  (size_t)na * max_per_agent * sizeof(u64),
                                  hipMemcpyDeviceToHost, stream_));
       HIP_CHECK(hipStreamSynchronize(stream_));
     }
-    std::memcpy(counts.mutable_data(), h_out_counts_, na * sizeof(u32));
-    if (return_seqs)
-      std::memcpy(seqs.mutable_data(), h_out_seqs_,
-                  (size_t)na * max_per_agent * sizeof(u64));
-    last_recv_na_ = na;
-    last_recv_K_ = max_per_agent;
-    return py::make_tuple(counts, seqs);
+    return received(counts, seqs, na, max_per_agent);
   }
 
   // Deliver the payloads of the LAST receive_many/run_tick straight from
@@ -696,15 +467,12 @@ public:
       throw std::invalid_argument("offsets must match the last receive");
     if (max_count == 0 || (int)max_count > last_recv_K_)
       max_count = last_recv_K_;
-    if (stride == 0 || stride > g_.slot_bytes)
-      stride = g_.slot_bytes;
-    stride = (stride + 15u) & ~15u;
+    stride = clamp_stride(stride);
     if ((size_t)total * stride > (size_t)staging_batch_ * g_.slot_bytes)
       throw std::invalid_argument("delivery exceeds the pinned buffer");
     {
       py::gil_scoped_release nogil;
-      HIP_CHECK(hipEventRecord(ev_, stream_));
-      HIP_CHECK(hipStreamWaitEvent(copy_stream_, ev_, 0));
+      copy_after_main();
       HIP_CHECK(hipMemcpyAsync(d_unread_, offsets.data(),
                                last_recv_na_ * sizeof(u32),
                                hipMemcpyHostToDevice, copy_stream_));
@@ -716,14 +484,7 @@ public:
       HIP_CHECK(hipMemcpyAsync(h_fetch_pay_, d_fetch_pay_,
                                (size_t)total * stride, hipMemcpyDeviceToHost,
                                copy_stream_));
-      if (synchronize) {
-        HIP_CHECK(hipStreamSynchronize(copy_stream_));
-      } else {
-        HIP_CHECK(hipEventRecord(d2h_ev_[d2h_cur_], copy_stream_));
-        d2h_cur_ ^= 1;
-        HIP_CHECK(hipEventSynchronize(d2h_ev_[d2h_cur_]));
-        drain_spree();
-      }
+      finish_delivery(synchronize);
     }
     return (u64)total * stride;
   }
@@ -792,14 +553,12 @@ public:
                          reinterpret_cast<long long *>(seqs_ptr),
                          reinterpret_cast<int *>(lengths_ptr),
                          reinterpret_cast<int *>(agent_row_ptr), stride, g_);
-      HIP_CHECK(hipMemcpyAsync(h_out_counts_, d_out_counts_, na * sizeof(u32),
-                               hipMemcpyDeviceToHost, stream_));
+      counts_to_host(d_out_counts_, na);
       HIP_CHECK(hipStreamSynchronize(stream_));
     }
-    std::memcpy(counts.mutable_data(), h_out_counts_, na * sizeof(u32));
     last_recv_na_ = na;
     last_recv_K_ = max_per_agent;
-    return counts;
+    return host_counts(counts);
   }
 
   // Mark `n` messages, named by an int64 device array, with `status`
@@ -903,23 +662,7 @@ public:
       throw std::invalid_argument("fetch batch exceeds staging_batch");
     {
       py::gil_scoped_release nogil;
-      // order the gather after any in-flight enqueue on the main stream
-      HIP_CHECK(hipEventRecord(ev_, stream_));
-      HIP_CHECK(hipStreamWaitEvent(copy_stream_, ev_, 0));
-      HIP_CHECK(hipMemcpyAsync(d_seqs_in_, seqs.data(), n * sizeof(u64),
-                               hipMemcpyHostToDevice, copy_stream_));
-      hipLaunchKernelGGL(k_gather, dim3((n + 3) / 4), dim3(256), 0,
-                         copy_stream_, d_seqs_in_, n, d_hdr_, d_status_,
-                         d_payload_, d_fetch_hdr_, d_fetch_status_,
-                         d_fetch_pay_, evict_base_, g_.slot_bytes, g_);
-      HIP_CHECK(hipMemcpyAsync(h_fetch_hdr_, d_fetch_hdr_, n * sizeof(Rec),
-                               hipMemcpyDeviceToHost, copy_stream_));
-      HIP_CHECK(hipMemcpyAsync(h_fetch_status_, d_fetch_status_,
-                               n * sizeof(u32), hipMemcpyDeviceToHost,
-                               copy_stream_));
-      HIP_CHECK(hipMemcpyAsync(h_fetch_pay_, d_fetch_pay_,
-                               (size_t)n * g_.slot_bytes,
-                               hipMemcpyDeviceToHost, copy_stream_));
+      gather_to_host(seqs.data(), n, g_.slot_bytes, true);
       HIP_CHECK(hipStreamSynchronize(copy_stream_));
     }
     py::array_t<u32> status(n);
@@ -941,41 +684,15 @@ public:
       return 0;
     if ((u32)n > staging_batch_)
       throw std::invalid_argument("fetch batch exceeds staging_batch");
-    if (stride == 0 || stride > g_.slot_bytes)
-      stride = g_.slot_bytes;
-    stride = (stride + 15u) & ~15u;
+    stride = clamp_stride(stride);
+    py::gil_scoped_release nogil;
+    gather_to_host(seqs.data(), n, stride, false);
+    finish_delivery(synchronize);
+    if (!synchronize)
+      return (u64)n * stride; // upper bound; D2H still in flight
     u64 bytes = 0;
-    {
-      py::gil_scoped_release nogil;
-      HIP_CHECK(hipEventRecord(ev_, stream_));
-      HIP_CHECK(hipStreamWaitEvent(copy_stream_, ev_, 0));
-      HIP_CHECK(hipMemcpyAsync(d_seqs_in_, seqs.data(), n * sizeof(u64),
-                               hipMemcpyHostToDevice, copy_stream_));
-      hipLaunchKernelGGL(k_gather, dim3((n + 3) / 4), dim3(256), 0,
-                         copy_stream_, d_seqs_in_, n, d_hdr_, d_status_,
-                         d_payload_, d_fetch_hdr_, d_fetch_status_,
-                         d_fetch_pay_, evict_base_, stride, g_);
-      HIP_CHECK(hipMemcpyAsync(h_fetch_hdr_, d_fetch_hdr_, n * sizeof(Rec),
-                               hipMemcpyDeviceToHost, copy_stream_));
-      HIP_CHECK(hipMemcpyAsync(h_fetch_pay_, d_fetch_pay_,
-                               (size_t)n * stride,
-                               hipMemcpyDeviceToHost, copy_stream_));
-      if (synchronize) {
-        HIP_CHECK(hipStreamSynchronize(copy_stream_));
-        for (int i = 0; i < n; ++i)
-          bytes += h_fetch_hdr_[i].payload_len;
-      } else {
-        // bounded async pipeline: wait for the delivery issued two
-        // calls ago before letting this one fly (an unbounded copy
-        // stream backlog eventually hard-blocks the runtime for the
-        // whole accumulated drain)
-        HIP_CHECK(hipEventRecord(d2h_ev_[d2h_cur_], copy_stream_));
-        d2h_cur_ ^= 1;
-        HIP_CHECK(hipEventSynchronize(d2h_ev_[d2h_cur_]));
-        drain_spree();
-        bytes = (u64)n * stride; // upper bound; D2H still in flight
-      }
-    }
+    for (int i = 0; i < n; ++i)
+      bytes += h_fetch_hdr_[i].payload_len;
     return bytes;
   }
 
@@ -993,8 +710,7 @@ public:
       throw std::invalid_argument("status batch exceeds staging_batch");
     {
       py::gil_scoped_release nogil;
-      HIP_CHECK(hipEventRecord(ev_, stream_));
-      HIP_CHECK(hipStreamWaitEvent(copy_stream_, ev_, 0));
+      copy_after_main();
       HIP_CHECK(hipMemcpyAsync(d_seqs_in_, seqs.data(), n * sizeof(u64),
                                hipMemcpyHostToDevice, copy_stream_));
       hipLaunchKernelGGL(k_statuses, dim3((n + 255) / 256), dim3(256), 0,
@@ -1045,15 +761,8 @@ public:
   py::array_t<u64> query_range(u64 lo, u64 hi, int f_sender, int f_receiver,
                                int f_type, int f_status, double after,
                                double before, u32 pred_mask, u32 cap) {
-    if (lo < evict_base_)
-      lo = evict_base_;
-    if (hi > count_)
-      hi = count_;
-    if (cap > staging_batch_)
-      cap = staging_batch_;
-    if (lo >= hi)
+    if (!clamp_scan(lo, hi, cap))
       return py::array_t<u64>(0);
-    u32 nmatch = 0;
     {
       py::gil_scoped_release nogil;
       HIP_CHECK(hipMemsetAsync(d_match_count_, 0, sizeof(u32), stream_));
@@ -1063,16 +772,8 @@ public:
                          f_sender, f_receiver, f_type, f_status, after, before,
                          pred_mask, d_hdr_, d_status_, d_match_,
                          d_match_count_, cap, g_);
-      HIP_CHECK(hipMemcpyAsync(&nmatch, d_match_count_, sizeof(u32),
-                               hipMemcpyDeviceToHost, stream_));
-      HIP_CHECK(hipStreamSynchronize(stream_));
     }
-    const u32 take = nmatch < cap ? nmatch : cap;
-    py::array_t<u64> out(take);
-    if (take)
-      HIP_CHECK(hipMemcpy(out.mutable_data(), d_match_, take * sizeof(u64),
-                          hipMemcpyDeviceToHost));
-    return out;
+    return read_matches(cap);
   }
 
   py::array_t<u64> search_range(u64 lo, u64 hi, py::bytes needle, bool fold,
@@ -1080,15 +781,8 @@ public:
     std::string nd = needle;
     if (nd.empty() || nd.size() > 256)
       throw std::invalid_argument("needle must be 1..256 bytes");
-    if (lo < evict_base_)
-      lo = evict_base_;
-    if (hi > count_)
-      hi = count_;
-    if (cap > staging_batch_)
-      cap = staging_batch_;
-    if (lo >= hi)
+    if (!clamp_scan(lo, hi, cap))
       return py::array_t<u64>(0);
-    u32 nmatch = 0;
     {
       py::gil_scoped_release nogil;
       HIP_CHECK(hipMemcpyAsync(d_needle_, nd.data(), nd.size(),
@@ -1132,16 +826,8 @@ public:
                            fold ? 1 : 0, d_hdr_, d_status_, d_payload_,
                            d_match_, d_match_count_, cap, g_);
       }
-      HIP_CHECK(hipMemcpyAsync(&nmatch, d_match_count_, sizeof(u32),
-                               hipMemcpyDeviceToHost, stream_));
-      HIP_CHECK(hipStreamSynchronize(stream_));
     }
-    const u32 take = nmatch < cap ? nmatch : cap;
-    py::array_t<u64> out(take);
-    if (take)
-      HIP_CHECK(hipMemcpy(out.mutable_data(), d_match_, take * sizeof(u64),
-                          hipMemcpyDeviceToHost));
-    return out;
+    return read_matches(cap);
   }
 
   // Inbox window for history listing (peek): returns (wpos, entries).
@@ -1180,12 +866,10 @@ public:
       hipLaunchKernelGGL(k_unread, dim3(na), dim3(256), 0, stream_, d_agents_,
                          na, evict_base_, d_status_, d_inbox_, d_wpos_,
                          d_unread_, g_);
-      HIP_CHECK(hipMemcpyAsync(h_out_counts_, d_unread_, na * sizeof(u32),
-                               hipMemcpyDeviceToHost, stream_));
+      counts_to_host(d_unread_, na);
       HIP_CHECK(hipStreamSynchronize(stream_));
     }
-    std::memcpy(out.mutable_data(), h_out_counts_, na * sizeof(u32));
-    return out;
+    return host_counts(out);
   }
 
   // ---- counters / stats ----
@@ -1333,12 +1017,107 @@ public:
   // ---- accessors ----
   u64 total_messages() const { return count_; }
   u64 evict_base() const { return evict_base_; }
-  u32 staging_batch() const { return staging_batch_; }
-  u32 slot_bytes() const { return g_.slot_bytes; }
-  u32 recv_window() const { return g_.recv_window; }
   size_t out_pool() const { return out_pool_; }
 
 private:
+  std::array<hipStream_t *, 4> streams() {
+    return {&stream_, &copy_stream_, &h2d_stream_, &lb_stream_};
+  }
+
+  static void new_event(hipEvent_t &e) {
+    HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  }
+
+  // Everything the queue owns, made in one fixed order: the position of
+  // each buffer matters to the measured paths (profiles/device_send.md),
+  // so new buffers go at the end. Buffers made without a fill value are
+  // written before they are read.
+  void init(u32 num_slots, u32 slot_bytes, u32 max_agents, u32 inbox_capacity,
+            u32 num_bitmaps, u32 num_backends, u32 staging_batch) {
+    HIP_CHECK(hipSetDevice(device_));
+    for (hipStream_t *s : streams())
+      HIP_CHECK(hipStreamCreateWithFlags(s, hipStreamNonBlocking));
+    for (hipEvent_t *e :
+         {&ev_, &up_ev_[0], &up_ev_[1], &d2h_ev_[0], &d2h_ev_[1]})
+      new_event(*e);
+
+    // device state
+    buf_.dev_alloc(d_hdr_, num_slots);
+    buf_.dev_alloc(d_status_, num_slots, 0);
+    buf_.dev_alloc(d_payload_, (size_t)num_slots * slot_bytes);
+    buf_.dev_alloc(d_inbox_, (size_t)max_agents * inbox_capacity);
+    buf_.dev_alloc(d_wpos_, max_agents, 0);
+    buf_.dev_alloc(d_rpos_, max_agents, 0);
+    buf_.dev_alloc(d_carry_, (size_t)max_agents * g_.recv_window);
+    buf_.dev_alloc(d_carry_n_, max_agents, 0);
+    buf_.dev_alloc(d_active_, max_agents, 0);
+    buf_.dev_alloc(d_bitmaps_, (size_t)num_bitmaps * g_.bitmap_words);
+    buf_.dev_alloc(d_bitmap_epochs_, num_bitmaps, 0xFF); // all EPOCH_NONE
+    buf_.dev_alloc(d_dropped_, 1, 0);
+    buf_.dev_alloc(d_by_type_, N_TYPES, 0);
+    buf_.dev_alloc(d_by_status_, N_STATUS, 0);
+    buf_.dev_alloc(d_sent_, max_agents, 0);
+    buf_.dev_alloc(d_received_, max_agents, 0);
+    buf_.dev_alloc(d_bcast_, staging_batch);
+    buf_.dev_alloc(d_bcast_count_, 1);
+    buf_.dev_alloc(d_backend_loads_, num_backends, 0);
+    buf_.dev_alloc(d_choices_, staging_batch);
+    buf_.dev_alloc(d_lb_out_, staging_batch);
+    buf_.dev_alloc(d_match_, staging_batch);
+    buf_.dev_alloc(d_match_count_, 1);
+    buf_.dev_alloc(d_needle_, 256);
+    buf_.dev_alloc(d_agents_, max_agents);
+    buf_.dev_alloc(d_unread_, max_agents);
+
+    buf_.dev_alloc(d_dyn_, 2);
+    buf_.dev_alloc(d_tail_, 1, 0);
+    out_pool_ = (size_t)4 << 20; // receive output pool: 4M entries, 32 MB
+    buf_.dev_alloc(d_out_seqs_, out_pool_);
+    buf_.dev_alloc(d_out_counts_, max_agents);
+
+    // staging (device side of the H2D batch), double-buffered so the
+    // host can fill batch i+1 while batch i's H2D/kernels run
+    stage_pay_bytes_ = (size_t)staging_batch * 1024; // grows on demand
+    for (int s = 0; s < 2; ++s) {
+      buf_.dev_alloc(d_stage_recs_[s], staging_batch);
+      buf_.dev_alloc(d_stage_pay_[s], stage_pay_bytes_);
+      new_event(stage_ev_[s]);
+    }
+    buf_.dev_alloc(d_seqs_in_, staging_batch);
+    buf_.dev_alloc(d_fetch_hdr_, staging_batch);
+    buf_.dev_alloc(d_fetch_status_, staging_batch);
+    buf_.dev_alloc(d_fetch_pay_, (size_t)staging_batch * slot_bytes);
+
+    // pinned host staging
+    for (int s = 0; s < 2; ++s) {
+      buf_.host_alloc(h_recs_[s], staging_batch);
+      buf_.host_alloc(h_pay_[s], stage_pay_bytes_);
+    }
+    buf_.host_alloc(h_out_seqs_, out_pool_);
+    buf_.host_alloc(h_out_counts_, max_agents);
+    buf_.host_alloc(h_fetch_hdr_, staging_batch);
+    buf_.host_alloc(h_fetch_status_, staging_batch);
+    buf_.host_alloc(h_fetch_pay_, (size_t)staging_batch * slot_bytes);
+    buf_.host_alloc(h_choices_, staging_batch);
+
+    // device-resident send: sanitised records, and the per-workgroup
+    // reply counts / offsets of the compaction (256 rows per workgroup).
+    // Allocated last, so that every buffer above sits where it did
+    // before these existed (profiles/device_send.md)
+    const size_t reply_blocks = ((size_t)staging_batch + 255) / 256;
+    buf_.dev_alloc(d_dev_recs_, staging_batch);
+    buf_.dev_alloc(d_reply_blk_, reply_blocks);
+    buf_.dev_alloc(d_reply_off_, reply_blocks + 1);
+    buf_.host_alloc(h_reply_m_, 1);
+
+    // device-resident dispatch: the device copy of the pins (one word per
+    // polled agent) and the per-backend row counts with their pinned
+    // landing buffer. Last again, for the same reason
+    buf_.dev_alloc(d_disp_pinned_, max_agents);
+    buf_.dev_alloc(d_disp_counts_, 64);
+    buf_.host_alloc(h_disp_counts_, 64);
+  }
+
   void check_dispatch_backends(int n_backends) const {
     if (n_backends < 1 || n_backends > 64 ||
         (u32)n_backends > g_.num_backends)
@@ -1374,17 +1153,19 @@ private:
   }
 
   // Launch the enqueue kernel pair (+ fan-out) for n records at
-  // `recs`/`pay` (device pointers) with host-known base seq; async on
-  // stream_. Callers already reset d_bcast_count_.
-  void launch_enqueue(const Rec *recs, const u8 *pay, int n, u64 base) {
+  // `recs`/`pay` (device pointers); async on stream_. `dyn` (the captured
+  // tick) overrides the host-known base seq. The broadcast count is reset
+  // first unless the caller has done so (`reset_bcast`).
+  void launch_enqueue(const Rec *recs, const u8 *pay, int n, u64 base,
+                      const u64 *dyn = nullptr, bool reset_bcast = true) {
+    if (reset_bcast)
+      HIP_CHECK(hipMemsetAsync(d_bcast_count_, 0, sizeof(u32), stream_));
     hipLaunchKernelGGL(k_enqueue_meta, dim3((n + 255) / 256), dim3(256), 0,
-                       stream_, recs, n, base, (const u64 *)nullptr, d_hdr_,
-                       d_status_, d_inbox_, d_wpos_, d_rpos_, d_by_type_,
-                       d_by_status_, d_sent_, d_bcast_, d_bcast_count_,
-                       d_dropped_, g_);
+                       stream_, recs, n, base, dyn, d_hdr_, d_status_,
+                       d_inbox_, d_wpos_, d_rpos_, d_by_type_, d_by_status_,
+                       d_sent_, d_bcast_, d_bcast_count_, d_dropped_, g_);
     hipLaunchKernelGGL(k_enqueue_payload, dim3((n + 3) / 4), dim3(256), 0,
-                       stream_, recs, pay, n, base, (const u64 *)nullptr,
-                       d_payload_, g_);
+                       stream_, recs, pay, n, base, dyn, d_payload_, g_);
     hipLaunchKernelGGL(k_fanout, dim3((g_.max_agents + 255) / 256), dim3(256),
                        0, stream_, d_bcast_, d_bcast_count_, d_active_,
                        d_hdr_, d_bitmaps_, d_bitmap_epochs_, d_inbox_,
@@ -1406,6 +1187,174 @@ private:
   void check_agent(u32 idx) const {
     if (idx >= g_.max_agents)
       throw std::out_of_range("agent index out of range");
+  }
+
+  static bool bad_slot(int slot) { return slot < 0 || slot > 1; }
+
+  static void check_slot(int slot) {
+    if (bad_slot(slot))
+      throw std::invalid_argument("slot must be 0 or 1");
+  }
+
+  void check_batch(int n) const {
+    if ((u32)n > staging_batch_)
+      throw std::invalid_argument("batch exceeds staging_batch");
+  }
+
+  // ---- staging slots ----
+
+  // Copy a batch into a slot's pinned buffers. The one place that writes
+  // them: it waits for the H2D that may still read them, and it forgets
+  // an earlier prefetch, so a refilled slot is uploaded again.
+  void fill_slot(int slot, const py::buffer_info &ri,
+                 const py::buffer_info &pi, int n) {
+    const size_t pay_bytes = (size_t)pi.size * pi.itemsize;
+    ensure_stage_pay(pay_bytes + 16);
+    {
+      py::gil_scoped_release nogil;
+      HIP_CHECK(hipEventSynchronize(stage_ev_[slot]));
+      std::memcpy(h_recs_[slot], ri.ptr, (size_t)n * sizeof(Rec));
+      if (pay_bytes)
+        par_memcpy(h_pay_[slot], pi.ptr, pay_bytes);
+    }
+    staged_n_[slot] = n;
+    staged_pay_[slot] = pay_bytes;
+    uploaded_[slot] = false;
+  }
+
+  // H2D of a slot's staged_n_ records and staged_pay_ bytes from pinned
+  // `recs` / `pay` on `s`; stage_ev_ marks the pinned side free again.
+  void upload_slot(int slot, const void *recs, const void *pay,
+                   hipStream_t s) {
+    HIP_CHECK(hipMemcpyAsync(d_stage_recs_[slot], recs,
+                             (size_t)staged_n_[slot] * sizeof(Rec),
+                             hipMemcpyHostToDevice, s));
+    if (staged_pay_[slot])
+      HIP_CHECK(hipMemcpyAsync(d_stage_pay_[slot], pay, staged_pay_[slot],
+                               hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipEventRecord(stage_ev_[slot], s));
+  }
+
+  // The same on the H2D stream, left for wait_prefetch to pick up.
+  void prefetch_slot(int slot, const void *recs, const void *pay) {
+    upload_slot(slot, recs, pay, h2d_stream_);
+    HIP_CHECK(hipEventRecord(up_ev_[slot], h2d_stream_));
+    uploaded_[slot] = true;
+  }
+
+  // Order stream_ after a slot's prefetch, if there was one.
+  bool wait_prefetch(int slot) {
+    if (!uploaded_[slot])
+      return false;
+    HIP_CHECK(hipStreamWaitEvent(stream_, up_ev_[slot], 0));
+    uploaded_[slot] = false;
+    return true;
+  }
+
+  // ---- receive / delivery sequences ----
+
+  // Per-agent counts at `d_src` into the pinned landing buffer, async on
+  // stream_; host_counts copies them out after the sync.
+  void counts_to_host(const u32 *d_src, int na) {
+    HIP_CHECK(hipMemcpyAsync(h_out_counts_, d_src, na * sizeof(u32),
+                             hipMemcpyDeviceToHost, stream_));
+  }
+
+  // The arrays are made by the caller before it launches, while the GPU
+  // still has earlier work to do, not here on the critical path.
+  py::array_t<u32> host_counts(py::array_t<u32> counts) const {
+    std::memcpy(counts.mutable_data(), h_out_counts_,
+                counts.size() * sizeof(u32));
+    return counts;
+  }
+
+  // (counts, seqs) of the na x K receive that just landed in the pinned
+  // buffers (`seqs` is empty when they were not asked for); it becomes
+  // the one deliver_outbuf serves.
+  py::tuple received(py::array_t<u32> counts, py::array_t<u64> seqs, int na,
+                     int K) {
+    std::memcpy(seqs.mutable_data(), h_out_seqs_, seqs.size() * sizeof(u64));
+    last_recv_na_ = na;
+    last_recv_K_ = K;
+    return py::make_tuple(host_counts(counts), seqs);
+  }
+
+  // Order copy_stream_ after whatever stream_ holds (an in-flight enqueue
+  // or receive).
+  void copy_after_main() {
+    HIP_CHECK(hipEventRecord(ev_, stream_));
+    HIP_CHECK(hipStreamWaitEvent(copy_stream_, ev_, 0));
+  }
+
+  // D2H row stride of a host delivery: 0 or too large means slot_bytes,
+  // rounded up to the 16-B chunk the gather kernels copy.
+  u32 clamp_stride(u32 stride) const {
+    if (stride == 0 || stride > g_.slot_bytes)
+      stride = g_.slot_bytes;
+    return (stride + 15u) & ~15u;
+  }
+
+  // k_gather of `n` seqs and the D2H of their headers, statuses (if
+  // asked) and `stride`-byte payload rows, on copy_stream_ after stream_.
+  void gather_to_host(const u64 *seqs, int n, u32 stride, bool with_status) {
+    copy_after_main();
+    HIP_CHECK(hipMemcpyAsync(d_seqs_in_, seqs, n * sizeof(u64),
+                             hipMemcpyHostToDevice, copy_stream_));
+    hipLaunchKernelGGL(k_gather, dim3((n + 3) / 4), dim3(256), 0, copy_stream_,
+                       d_seqs_in_, n, d_hdr_, d_status_, d_payload_,
+                       d_fetch_hdr_, d_fetch_status_, d_fetch_pay_, evict_base_,
+                       stride, g_);
+    HIP_CHECK(hipMemcpyAsync(h_fetch_hdr_, d_fetch_hdr_, n * sizeof(Rec),
+                             hipMemcpyDeviceToHost, copy_stream_));
+    if (with_status)
+      HIP_CHECK(hipMemcpyAsync(h_fetch_status_, d_fetch_status_,
+                               n * sizeof(u32), hipMemcpyDeviceToHost,
+                               copy_stream_));
+    HIP_CHECK(hipMemcpyAsync(h_fetch_pay_, d_fetch_pay_, (size_t)n * stride,
+                             hipMemcpyDeviceToHost, copy_stream_));
+  }
+
+  // End of a delivery on copy_stream_: drain it, or keep a bounded async
+  // pipeline: wait for the delivery issued two calls ago before letting
+  // this one fly (an unbounded copy stream backlog eventually hard-blocks
+  // the runtime for the whole accumulated drain).
+  void finish_delivery(bool synchronize) {
+    if (synchronize) {
+      HIP_CHECK(hipStreamSynchronize(copy_stream_));
+      return;
+    }
+    HIP_CHECK(hipEventRecord(d2h_ev_[d2h_cur_], copy_stream_));
+    d2h_cur_ ^= 1;
+    HIP_CHECK(hipEventSynchronize(d2h_ev_[d2h_cur_]));
+    drain_spree();
+  }
+
+  // ---- scans ----
+
+  // [lo, hi) cut to the live window and `cap` to the match buffer; false
+  // when nothing is left to scan.
+  bool clamp_scan(u64 &lo, u64 &hi, u32 &cap) const {
+    lo = std::max(lo, evict_base_);
+    hi = std::min(hi, count_);
+    cap = std::min(cap, staging_batch_);
+    return lo < hi;
+  }
+
+  // The matches a scan on stream_ left in d_match_ (at most `cap`).
+  py::array_t<u64> read_matches(u32 cap) {
+    u32 nmatch = 0;
+    {
+      py::gil_scoped_release nogil;
+      HIP_CHECK(hipMemcpyAsync(&nmatch, d_match_count_, sizeof(u32),
+                               hipMemcpyDeviceToHost, stream_));
+      HIP_CHECK(hipStreamSynchronize(stream_));
+    }
+    const u32 take = std::min(nmatch, cap);
+    py::array_t<u64> out(take);
+    if (take)
+      HIP_CHECK(hipMemcpy(out.mutable_data(), d_match_, take * sizeof(u64),
+                          hipMemcpyDeviceToHost));
+    return out;
   }
 
   // row stride of a device-side payload tensor: the bounds of a
@@ -1468,11 +1417,13 @@ private:
     HIP_CHECK(hipStreamSynchronize(stream_));
     HIP_CHECK(hipStreamSynchronize(h2d_stream_));
     HIP_CHECK(hipStreamSynchronize(copy_stream_));
+    // freed and made again through buf_, which forgets the old pointers
+    // and records the new ones: release() never sees a freed buffer
     for (int s = 0; s < 2; ++s) {
-      HIP_CHECK(hipFree(d_stage_pay_[s]));
-      (void)hipHostFree(h_pay_[s]);
-      HIP_CHECK(hipMalloc(&d_stage_pay_[s], nb));
-      HIP_CHECK(hipHostMalloc(&h_pay_[s], nb));
+      buf_.dev_free(d_stage_pay_[s]);
+      buf_.host_free(h_pay_[s]);
+      buf_.dev_alloc(d_stage_pay_[s], nb);
+      buf_.host_alloc(h_pay_[s], nb);
     }
     stage_pay_bytes_ = nb;
   }
@@ -1489,6 +1440,7 @@ private:
   size_t out_pool_ = 0;
   size_t stage_pay_bytes_ = 0;
 
+  HipBuffers buf_; // owns every d_* / h_* buffer below
   hipStream_t stream_{}, copy_stream_{}, h2d_stream_{}, lb_stream_{};
   hipEvent_t ev_{};
   hipEvent_t up_ev_[2] = {};

@@ -142,61 +142,26 @@ public:
     dg_.sub_cap = sub_cap;
     dg_.n_agents = n_agents;
     dg_.ring_cap = ring_cap;
-    HIP_CHECK(hipSetDevice(device_));
-    HIP_CHECK(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
-    const unsigned flags = hipHostMallocCoherent | hipHostMallocMapped;
-    HIP_CHECK(hipHostMalloc((void **)&h_ctrl_, DB_NWORDS * sizeof(ull), flags));
-    HIP_CHECK(hipHostMalloc((void **)&h_sub_recs_,
-                            (size_t)sub_cap * sizeof(Rec), flags));
-    HIP_CHECK(hipHostMalloc((void **)&h_sub_pay_,
-                            (size_t)sub_cap * slot_bytes, flags));
-    HIP_CHECK(hipHostMalloc((void **)&h_del_recs_,
-                            (size_t)n_agents * ring_cap * sizeof(Rec), flags));
-    HIP_CHECK(hipHostMalloc((void **)&h_del_pay_,
-                            (size_t)n_agents * ring_cap * slot_bytes, flags));
-    HIP_CHECK(hipHostMalloc((void **)&h_del_count_,
-                            (size_t)n_agents * sizeof(ull), flags));
-    HIP_CHECK(hipHostMalloc((void **)&h_del_rpos_,
-                            (size_t)n_agents * sizeof(ull), flags));
-    std::memset((void *)h_ctrl_, 0, DB_NWORDS * sizeof(ull));
-    std::memset((void *)h_del_count_, 0, (size_t)n_agents * sizeof(ull));
-    std::memset((void *)h_del_rpos_, 0, (size_t)n_agents * sizeof(ull));
-    // device-private per-agent delivery cursor + host-read-pos cache
-    // (only the kernel touches these)
-    HIP_CHECK(hipMalloc(&d_del_next_, (size_t)n_agents * sizeof(ull)));
-    HIP_CHECK(hipMemset(d_del_next_, 0, (size_t)n_agents * sizeof(ull)));
-    HIP_CHECK(hipMalloc(&d_del_rcache_, (size_t)n_agents * sizeof(ull)));
-    HIP_CHECK(hipMemset(d_del_rcache_, 0, (size_t)n_agents * sizeof(ull)));
-    read_pos_.assign(n_agents, 0);
-    HIP_CHECK(hipHostGetDevicePointer((void **)&m_ctrl_, (void *)h_ctrl_, 0));
-    HIP_CHECK(hipHostGetDevicePointer((void **)&m_sub_recs_, h_sub_recs_, 0));
-    HIP_CHECK(hipHostGetDevicePointer((void **)&m_sub_pay_, h_sub_pay_, 0));
-    HIP_CHECK(hipHostGetDevicePointer((void **)&m_del_recs_, h_del_recs_, 0));
-    HIP_CHECK(hipHostGetDevicePointer((void **)&m_del_pay_, h_del_pay_, 0));
-    HIP_CHECK(
-        hipHostGetDevicePointer((void **)&m_del_count_, (void *)h_del_count_, 0));
-    HIP_CHECK(
-        hipHostGetDevicePointer((void **)&m_del_rpos_, (void *)h_del_rpos_, 0));
+    try {
+      init(slot_bytes, sub_cap, n_agents, ring_cap);
+    } catch (...) {
+      release(); // the destructor of a half-built object never runs
+      throw;
+    }
   }
 
   ~DoorbellQueue() { release(); }
 
+  // Idempotent, and tolerant of a constructor that threw part-way.
   void release() {
     if (released_)
       return;
     released_ = true;
     if (running_)
       stop();
-    (void)hipStreamDestroy(stream_);
-    (void)hipFree(d_del_next_);
-    (void)hipFree(d_del_rcache_);
-    (void)hipHostFree((void *)h_del_rpos_);
-    (void)hipHostFree((void *)h_ctrl_);
-    (void)hipHostFree(h_sub_recs_);
-    (void)hipHostFree(h_sub_pay_);
-    (void)hipHostFree(h_del_recs_);
-    (void)hipHostFree(h_del_pay_);
-    (void)hipHostFree((void *)h_del_count_);
+    if (stream_)
+      (void)hipStreamDestroy(stream_);
+    buf_.free_all();
   }
 
   void start(double max_seconds = 60.0) {
@@ -330,6 +295,33 @@ public:
   }
 
 private:
+  // A coherent, mapped pinned block and its device-visible address.
+  template <class T> void mapped_alloc(T *&h, T *&m, size_t count) {
+    buf_.host_alloc(h, count, hipHostMallocCoherent | hipHostMallocMapped);
+    HIP_CHECK(hipHostGetDevicePointer((void **)&m, (void *)h, 0));
+  }
+
+  void init(u32 slot_bytes, u32 sub_cap, u32 n_agents, u32 ring_cap) {
+    HIP_CHECK(hipSetDevice(device_));
+    HIP_CHECK(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
+    mapped_alloc(h_ctrl_, m_ctrl_, DB_NWORDS);
+    mapped_alloc(h_sub_recs_, m_sub_recs_, sub_cap);
+    mapped_alloc(h_sub_pay_, m_sub_pay_, (size_t)sub_cap * slot_bytes);
+    mapped_alloc(h_del_recs_, m_del_recs_, (size_t)n_agents * ring_cap);
+    mapped_alloc(h_del_pay_, m_del_pay_,
+                 (size_t)n_agents * ring_cap * slot_bytes);
+    mapped_alloc(h_del_count_, m_del_count_, n_agents);
+    mapped_alloc(h_del_rpos_, m_del_rpos_, n_agents);
+    std::memset((void *)h_ctrl_, 0, DB_NWORDS * sizeof(ull));
+    std::memset((void *)h_del_count_, 0, (size_t)n_agents * sizeof(ull));
+    std::memset((void *)h_del_rpos_, 0, (size_t)n_agents * sizeof(ull));
+    // device-private per-agent delivery cursor + host-read-pos cache
+    // (only the kernel touches these)
+    buf_.dev_alloc(d_del_next_, n_agents, 0);
+    buf_.dev_alloc(d_del_rcache_, n_agents, 0);
+    read_pos_.assign(n_agents, 0);
+  }
+
   u64 h_ctrl_exited_safe_count(u32 agent) const {
     return ((volatile ull *)h_del_count_)[agent];
   }
@@ -340,6 +332,7 @@ private:
   bool released_ = false;
   u64 sub_head_ = 0;
   hipStream_t stream_{};
+  HipBuffers buf_; // owns the h_* and d_* buffers below
   volatile ull *h_ctrl_{};
   Rec *h_sub_recs_{};
   u8 *h_sub_pay_{};

@@ -49,7 +49,6 @@ PYBIND11_MODULE(_swarmq, m) {
       .def("deregister_agent", &DeviceQueue::deregister_agent)
       .def("active_agents", &DeviceQueue::active_agents)
       .def("enqueue_batch", &DeviceQueue::enqueue_batch)
-      .def("enqueue_batch_async", &DeviceQueue::enqueue_batch_async)
       .def("sync", &DeviceQueue::sync)
       .def("stage_fill", &DeviceQueue::stage_fill)
       .def("enqueue_staged", &DeviceQueue::enqueue_staged)
@@ -115,9 +114,6 @@ PYBIND11_MODULE(_swarmq, m) {
            py::arg("added_ptr"), py::arg("n_backends"))
       .def("total_messages", &DeviceQueue::total_messages)
       .def("evict_base", &DeviceQueue::evict_base)
-      .def("staging_batch", &DeviceQueue::staging_batch)
-      .def("slot_bytes", &DeviceQueue::slot_bytes)
-      .def("recv_window", &DeviceQueue::recv_window)
       .def("out_pool", &DeviceQueue::out_pool)
       .def("release", &DeviceQueue::release);
 

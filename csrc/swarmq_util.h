@@ -9,6 +9,7 @@
 #include <pybind11/stl.h>
 
 #include <algorithm>
+#include <array>
 #include <atomic>
 #include <chrono>
 #include <cstdlib>
@@ -57,6 +58,54 @@ static void par_memcpy(void *dst, const void *src, size_t n) {
   for (auto &t : ts)
     t.join();
 }
+
+// The device and pinned buffers of one queue object. A buffer is recorded
+// where it is allocated and free_all() frees what was recorded, so a
+// buffer cannot be made without an owner; a constructor that throws
+// part-way frees what it had made through the same walk. A buffer that
+// is regrown goes through dev_free / host_free and back through
+// dev_alloc / host_alloc: the freed pointer leaves the record (and the
+// member is nulled), the new one enters it.
+struct HipBuffers {
+  std::vector<void *> dev, host;
+
+  // `count` elements of T; every byte set to `fill` unless it is negative
+  template <class T> void dev_alloc(T *&p, size_t count, int fill = -1) {
+    dev.emplace_back(); // the record exists before the buffer does
+    HIP_CHECK(hipMalloc(&dev.back(), count * sizeof(T)));
+    p = (T *)dev.back();
+    if (fill >= 0)
+      HIP_CHECK(hipMemset(dev.back(), fill, count * sizeof(T)));
+  }
+
+  template <class T>
+  void host_alloc(T *&p, size_t count, unsigned flags = hipHostMallocDefault) {
+    host.emplace_back();
+    HIP_CHECK(hipHostMalloc(&host.back(), count * sizeof(T), flags));
+    p = (T *)host.back();
+  }
+
+  template <class T> void dev_free(T *&p) {
+    dev.erase(std::remove(dev.begin(), dev.end(), (void *)p), dev.end());
+    (void)hipFree((void *)p);
+    p = nullptr;
+  }
+
+  template <class T> void host_free(T *&p) {
+    host.erase(std::remove(host.begin(), host.end(), (void *)p), host.end());
+    (void)hipHostFree((void *)p);
+    p = nullptr;
+  }
+
+  void free_all() {
+    for (void *p : dev)
+      (void)hipFree(p);
+    for (void *p : host)
+      (void)hipHostFree(p);
+    dev.clear();
+    host.clear();
+  }
+};
 
 // ---- device helpers ---- The row copies are one wavefront per row, 64
 // lanes x 16 B per round. No helper decides what to trust: the calling

@@ -113,6 +113,12 @@ class GpuEngine(Engine):
     def active_agents(self) -> np.ndarray:
         return self.q.active_agents().astype(bool)
 
+    def _chunks(self, n: int):
+        """(start, stop) pairs that cover ``range(n)`` in pieces of at most
+        ``staging_batch``, the most one binding call takes."""
+        for start in range(0, n, self._staging):
+            yield start, min(start + self._staging, n)
+
     # --- send plane ---
 
     def _pack_aligned(self, recs: np.ndarray, payloads: bytes):
@@ -175,27 +181,22 @@ class GpuEngine(Engine):
         pay_view = np.frombuffer(payloads, dtype=np.uint8)
         with self._lock:
             seqs = np.empty(n, dtype=np.uint64)
-            done = 0
-            while done < n:
-                chunk = min(self._staging, n - done)
-                sub = recs[done : done + chunk]
+            for a, b in self._chunks(n):
+                sub = recs[a:b]
                 # offsets need not be monotonic: bound the slice by the
                 # actual extremes
                 lo = int(sub["payload_off"].min())
                 hi = int(
                     (sub["payload_off"] + sub["payload_len"]).max()
                 )
-                if done or lo:
+                if a or lo:
                     sub = sub.copy()
                     sub["payload_off"] -= np.uint64(lo)
                 # numpy views via the buffer protocol: no bytes copies
                 base = self.q.enqueue_batch(
-                    sub, pay_view[lo : min(hi + 16, len(pay_view))], chunk
+                    sub, pay_view[lo : min(hi + 16, len(pay_view))], b - a
                 )
-                seqs[done : done + chunk] = np.arange(
-                    base, base + chunk, dtype=np.uint64
-                )
-                done += chunk
+                seqs[a:b] = np.arange(base, base + b - a, dtype=np.uint64)
             return seqs
 
     def alloc_bitmap(self, bits: np.ndarray) -> int:
@@ -423,15 +424,12 @@ class GpuEngine(Engine):
         torch.cuda.current_stream(dev).synchronize()
         hp, pp = headers.data_ptr(), payload.data_ptr()
         with self._lock:
-            base = done = 0
-            while done < n:
-                chunk = min(self._staging, n - done)
-                b = self.q.enqueue_from_device(
-                    hp + done * REC_DTYPE.itemsize, pp + done * stride,
-                    chunk, stride,
+            base = 0
+            for a, b in self._chunks(n):
+                first = self.q.enqueue_from_device(
+                    hp + a * REC_DTYPE.itemsize, pp + a * stride, b - a, stride,
                 )
-                base = b if done == 0 else base
-                done += chunk
+                base = base if a else first
         return np.arange(base, base + n, dtype=np.uint64)
 
     def reply_to_device(
@@ -474,17 +472,15 @@ class GpuEngine(Engine):
         hp, rp = delivery.headers.data_ptr(), delivery.agent_row.data_ptr()
         lp, pp = lengths.data_ptr(), payload.data_ptr()
         with self._lock:
-            base = m = done = 0
-            while done < total:
-                chunk = min(self._staging, total - done)
-                b, mc = self.q.reply_from_device(
-                    hp + done * REC_DTYPE.itemsize, rp + done * 4,
-                    lp + done * 4, pp + done * rstride, chunk, rstride,
+            base = m = 0
+            for a, b in self._chunks(total):
+                first, mc = self.q.reply_from_device(
+                    hp + a * REC_DTYPE.itemsize, rp + a * 4, lp + a * 4,
+                    pp + a * rstride, b - a, rstride,
                     agent_idxs, code, prio, flags, ts,
                 )
-                base = b if done == 0 else base
+                base = base if a else first
                 m += int(mc)
-                done += chunk
         return np.arange(base, base + m, dtype=np.uint64)
 
     def peek_inbox(self, agent_idx: int) -> np.ndarray:
@@ -498,11 +494,7 @@ class GpuEngine(Engine):
         if len(entries) == 0:
             return entries
         # drop tombstoned
-        st = self._statuses(entries)
-        return entries[st != ST_DELETED]
-
-    def _statuses(self, seqs: np.ndarray) -> np.ndarray:
-        return self.statuses(seqs)
+        return entries[self.statuses(entries) != ST_DELETED]
 
     def unread_count(self, agent_idx: int) -> int:
         out = self.q.unread_counts(np.array([agent_idx], dtype=np.uint32))
@@ -510,52 +502,46 @@ class GpuEngine(Engine):
 
     # --- message store ---
 
-    def fetch(self, seqs: np.ndarray) -> Tuple[np.ndarray, List[bytes]]:
+    def _fetch(self, seqs: np.ndarray, keep) -> np.ndarray:
+        """Headers, statuses and seqs of ``seqs`` as one _FETCH_DTYPE
+        array, a chunk at a time; ``keep(a, b, hdr, pay_b)`` takes each
+        chunk's payload rows (``slot_bytes`` apart in ``pay_b``)."""
         seqs = np.ascontiguousarray(seqs, dtype=np.uint64)
-        n = len(seqs)
-        out = np.zeros(n, dtype=_FETCH_DTYPE)
-        pays: List[bytes] = []
-        done = 0
-        while done < n:
-            chunk = min(self._staging, n - done)
-            sub = seqs[done : done + chunk]
-            hdr_b, status, pay_b = self.q.fetch(sub)
-            hdr = np.frombuffer(hdr_b, dtype=REC_DTYPE, count=chunk)
+        out = np.zeros(len(seqs), dtype=_FETCH_DTYPE)
+        for a, b in self._chunks(len(seqs)):
+            hdr_b, status, pay_b = self.q.fetch(seqs[a:b])
+            hdr = np.frombuffer(hdr_b, dtype=REC_DTYPE, count=b - a)
             for name in REC_DTYPE.names:
-                out[name][done : done + chunk] = hdr[name]
-            out["status"][done : done + chunk] = status.astype(np.uint8)
-            out["seq"][done : done + chunk] = sub
-            sb = self._slot_bytes
+                out[name][a:b] = hdr[name]
+            out["status"][a:b] = status.astype(np.uint8)
+            out["seq"][a:b] = seqs[a:b]
+            keep(a, b, hdr, pay_b)
+        return out
+
+    def fetch(self, seqs: np.ndarray) -> Tuple[np.ndarray, List[bytes]]:
+        pays: List[bytes] = []
+        sb = self._slot_bytes
+
+        def keep(a, b, hdr, pay_b):
             lens = hdr["payload_len"]
             pays.extend(
-                pay_b[i * sb : i * sb + int(lens[i])] for i in range(chunk)
+                pay_b[i * sb : i * sb + int(lens[i])] for i in range(b - a)
             )
-            done += chunk
-        return out, pays
+
+        return self._fetch(seqs, keep), pays
 
     def fetch_raw_chunks(self, seqs: np.ndarray):
         """Device gather + one pinned D2H per chunk; no per-message
         Python objects (the binary-checkpoint hot path)."""
-        seqs = np.ascontiguousarray(seqs, dtype=np.uint64)
-        n = len(seqs)
         stride = self._slot_bytes
-        out = np.zeros(n, dtype=_FETCH_DTYPE)
-        flat = np.empty((n, stride), dtype=np.uint8)
-        done = 0
-        while done < n:
-            chunk = min(self._staging, n - done)
-            sub = seqs[done : done + chunk]
-            hdr_b, status, pay_b = self.q.fetch(sub)
-            hdr = np.frombuffer(hdr_b, dtype=REC_DTYPE, count=chunk)
-            for name in REC_DTYPE.names:
-                out[name][done : done + chunk] = hdr[name]
-            out["status"][done : done + chunk] = status.astype(np.uint8)
-            out["seq"][done : done + chunk] = sub
-            flat[done : done + chunk] = np.frombuffer(
-                pay_b, dtype=np.uint8, count=chunk * stride
-            ).reshape(chunk, stride)
-            done += chunk
-        return out, flat.reshape(-1), stride
+        flat = np.empty((len(seqs), stride), dtype=np.uint8)
+
+        def keep(a, b, hdr, pay_b):
+            flat[a:b] = np.frombuffer(
+                pay_b, dtype=np.uint8, count=(b - a) * stride
+            ).reshape(b - a, stride)
+
+        return self._fetch(seqs, keep), flat.reshape(-1), stride
 
     def read_bitmap(self, slot: int, epoch: int):
         ep, words = self.q.get_bitmap(int(slot))
@@ -578,18 +564,13 @@ class GpuEngine(Engine):
         Returns bytes landed (an upper bound when async)."""
         seqs = np.ascontiguousarray(seqs, dtype=np.uint64)
         n = len(seqs)
-        done = 0
         total = 0
-        while done < n:
-            chunk = min(self._staging, n - done)
-            last = done + chunk >= n
+        for a, b in self._chunks(n):
             total += int(
                 self.q.fetch_raw(
-                    seqs[done : done + chunk], int(max_payload),
-                    synchronize and last,
+                    seqs[a:b], int(max_payload), synchronize and b >= n
                 )
             )
-            done += chunk
         return total
 
     def delivery_sync(self) -> None:
@@ -604,24 +585,14 @@ class GpuEngine(Engine):
     def set_statuses(self, seqs: np.ndarray, statuses: np.ndarray) -> None:
         seqs = np.ascontiguousarray(seqs, dtype=np.uint64)
         statuses = np.ascontiguousarray(statuses, dtype=np.uint32)
-        done = 0
-        while done < len(seqs):
-            chunk = min(self._staging, len(seqs) - done)
-            self.q.set_statuses(
-                seqs[done : done + chunk], statuses[done : done + chunk]
-            )
-            done += chunk
+        for a, b in self._chunks(len(seqs)):
+            self.q.set_statuses(seqs[a:b], statuses[a:b])
 
     def statuses(self, seqs: np.ndarray) -> np.ndarray:
         seqs = np.ascontiguousarray(seqs, dtype=np.uint64)
         out = np.empty(len(seqs), dtype=np.uint8)
-        done = 0
-        while done < len(seqs):
-            chunk = min(self._staging, len(seqs) - done)
-            out[done : done + chunk] = self.q.get_statuses(
-                seqs[done : done + chunk]
-            ).astype(np.uint8)
-            done += chunk
+        for a, b in self._chunks(len(seqs)):
+            out[a:b] = self.q.get_statuses(seqs[a:b]).astype(np.uint8)
         return out
 
     def query(
@@ -648,59 +619,48 @@ class GpuEngine(Engine):
         if before is not None:
             mask |= 32
         limit = min(int(limit), self._staging)
-        total = self.q.total_messages()
-        eb = self.q.evict_base()
-        found: List[np.ndarray] = []
-        nfound = 0
-        hi = total
-        chunk = max(1 << 20, limit)
-        # scan newest chunks first until the limit fills; if a window
-        # overflows the match buffer the subset is arbitrary, so shrink
-        # the window until it fits (newest-first stays exact)
-        while hi > eb and nfound < limit:
-            lo = max(eb, hi - chunk)
-            seqs = self.q.query_range(
-                lo,
-                hi,
-                -1 if sender is None else int(sender),
-                -1 if receiver is None else int(receiver),
-                -1 if type_code is None else int(type_code),
-                -1 if status is None else int(status),
-                0.0 if after is None else float(after),
-                0.0 if before is None else float(before),
-                mask,
-                self._staging,
-            )
-            if len(seqs) >= self._staging and hi - lo > 1:
-                chunk = max(1, chunk // 4)
-                continue
-            seqs = np.sort(np.asarray(seqs, dtype=np.uint64))[::-1]
-            found.append(seqs)
-            nfound += len(seqs)
-            hi = lo
-        if not found:
-            return np.empty(0, dtype=np.uint64)
-        return np.concatenate(found)[:limit]
+        args = (
+            -1 if sender is None else int(sender),
+            -1 if receiver is None else int(receiver),
+            -1 if type_code is None else int(type_code),
+            -1 if status is None else int(status),
+            0.0 if after is None else float(after),
+            0.0 if before is None else float(before),
+            mask,
+            self._staging,
+        )
+        return self._scan_newest_first(
+            lambda lo, hi: self.q.query_range(lo, hi, *args),
+            max(1 << 20, limit), limit, np.sort,
+        )
 
     def search(self, needle: bytes, case_sensitive: bool, limit: int) -> np.ndarray:
-        limit = min(int(limit), self._staging)
-        total = self.q.total_messages()
+        # the linear-scan kernel may report a message once per matching
+        # chunk: np.unique dedups as it sorts
+        return self._scan_newest_first(
+            lambda lo, hi: self.q.search_range(
+                lo, hi, needle, not case_sensitive, self._staging
+            ),
+            1 << 20, min(int(limit), self._staging), np.unique,
+        )
+
+    def _scan_newest_first(self, scan, window: int, limit: int, order):
+        """Up to ``limit`` matches of ``scan(lo, hi)``, newest first.
+        Windows of ``window`` seqs are scanned from the newest down until
+        the limit fills; if a window overflows the match buffer the subset
+        is arbitrary, so the window shrinks until it fits (newest-first
+        stays exact). ``order`` sorts one window's matches ascending."""
         eb = self.q.evict_base()
+        hi = self.q.total_messages()
         found: List[np.ndarray] = []
         nfound = 0
-        hi = total
-        chunk = 1 << 20
         while hi > eb and nfound < limit:
-            lo = max(eb, hi - chunk)
-            seqs = self.q.search_range(
-                lo, hi, needle, not case_sensitive, self._staging
-            )
+            lo = max(eb, hi - window)
+            seqs = scan(lo, hi)
             if len(seqs) >= self._staging and hi - lo > 1:
-                chunk = max(1, chunk // 4)
+                window = max(1, window // 4)
                 continue
-            # the linear-scan kernel may report a message once per
-            # matching chunk: dedup
-            seqs = np.unique(np.asarray(seqs, dtype=np.uint64))[::-1]
+            seqs = order(np.asarray(seqs, dtype=np.uint64))[::-1]
             found.append(seqs)
             nfound += len(seqs)
             hi = lo

@@ -429,6 +429,124 @@ def test_staged_pipeline_roundtrip(gpu_engine):
         assert p == payloads[int(s)], int(s)
 
 
+def raw_queue(**kw):
+    """A small DeviceQueue without the engine around it."""
+    from swarmdb_amd import _swarmq
+
+    args = dict(num_slots=256, slot_bytes=512, max_agents=64,
+                inbox_capacity=256, num_bitmaps=4, num_backends=4,
+                staging_batch=64, device=0)
+    args.update(kw)
+    q = _swarmq.DeviceQueue(**args)
+    q.register_agent(0)
+    q.register_agent(1)
+    return q
+
+
+def raw_batch(seed, n, plen):
+    """n messages 0 -> 1 of plen bytes each (a multiple of 16)."""
+    recs, payload = make_batch(np.random.default_rng(seed), n, 1,
+                               payload_bytes=plen)
+    recs["sender"] = 0
+    recs["receiver"] = 1
+    return recs, np.frombuffer(payload, np.uint8)
+
+
+def assert_log_holds(q, base, recs, pay):
+    """Messages base.. of the log are exactly `recs` with their bytes."""
+    n = len(recs)
+    hdr_b, _, pay_b = q.fetch(np.arange(base, base + n, dtype=np.uint64))
+    hdr = np.frombuffer(hdr_b, dtype=REC_DTYPE)
+    for name in ("sender", "receiver", "type", "priority", "timestamp",
+                 "payload_len", "content_len"):
+        assert hdr[name].tolist() == recs[name].tolist(), name
+    for i in range(n):
+        off, ln = int(recs["payload_off"][i]), int(recs["payload_len"][i])
+        assert pay_b[i * 512 : i * 512 + ln] == pay[off : off + ln].tobytes(), i
+
+
+def assert_roundtrips_one(q):
+    recs, pay = raw_batch(5, 1, 64)
+    base = q.enqueue_batch(recs, pay, 1)
+    counts, seqs = q.receive_many(np.array([1], dtype=np.uint32), 4, False)
+    assert counts.tolist() == [1] and int(seqs[0]) == base
+    assert_log_holds(q, base, recs, pay)
+
+
+def test_refused_construction_leaves_nothing_behind():
+    """Each argument refusal raises with its message, and a valid queue
+    built right after them works."""
+    for kw, msg in (
+        (dict(slot_bytes=24), "slot_bytes must be a multiple of 16"),
+        (dict(max_agents=65), "max_agents must be a multiple of 64"),
+        (dict(recv_window=48), "recv_window must be a power of two >= 64"),
+    ):
+        with pytest.raises(ValueError) as e:
+            raw_queue(**kw)
+        assert str(e.value) == msg
+    q = raw_queue()
+    assert_roundtrips_one(q)
+    q.release()
+
+
+def test_refilled_slot_is_uploaded_again():
+    """stage_fill after a prefetch of the same slot: the enqueue uploads
+    the new batch instead of enqueueing the prefetched one under the new
+    count."""
+    q = raw_queue()
+    a_recs, a_pay = raw_batch(1, 8, 128)
+    b_recs, b_pay = raw_batch(2, 3, 48)
+    q.stage_fill(0, a_recs, a_pay, 8)
+    q.prefetch_staged(0)
+    q.stage_fill(0, b_recs, b_pay, 3)
+    base = q.enqueue_staged(0)
+    q.sync()
+    assert base == 0 and q.total_messages() == 3
+    assert_log_holds(q, 0, b_recs, b_pay)
+    q.release()
+
+
+def test_enqueue_batch_after_unsynchronized_staged_enqueue():
+    """enqueue_batch reuses slot 0 right behind an enqueue_staged(0) that
+    nobody waited for: the log holds both batches, in order."""
+    q = raw_queue()
+    a_recs, a_pay = raw_batch(3, 8, 128)
+    b_recs, b_pay = raw_batch(4, 5, 80)
+    q.stage_fill(0, a_recs, a_pay, 8)
+    base_a = q.enqueue_staged(0)
+    base_b = q.enqueue_batch(b_recs, b_pay, 5)
+    assert (base_a, base_b, q.total_messages()) == (0, 8, 13)
+    assert_log_holds(q, 0, a_recs, a_pay)
+    assert_log_holds(q, 8, b_recs, b_pay)
+    q.release()
+
+
+def test_release_twice_with_tick_graph_and_regrown_staging():
+    """release() is idempotent on a queue whose tick graph is built and
+    whose staging payload buffers were regrown, and `del` after it is
+    quiet; the next queue works."""
+    q = raw_queue()
+    recs, pay = raw_batch(6, 4, 64)
+    q.build_tick(4, np.array([1], dtype=np.uint32), 8, False)
+    q.stage_fill(0, recs, pay, 4)
+    q.prefetch_staged(0)
+    counts, _ = q.run_tick(0)
+    assert counts.tolist() == [4]
+    # one payload buffer larger than staging_batch * 1024 forces the regrow
+    big = np.zeros(64 * 1024 + 4096, dtype=np.uint8)
+    big[: len(pay)] = pay
+    q.stage_fill(1, recs, big, 4)
+    assert q.enqueue_staged(1) == 4
+    q.sync()
+    assert_log_holds(q, 4, recs, big)
+    q.release()
+    q.release()
+    del q
+    q = raw_queue()
+    assert_roundtrips_one(q)
+    q.release()
+
+
 def test_group_fanout_parity():
     """VIS_GROUP: one slot, member-only inbox entries — CPU vs GPU."""
     from swarmdb_amd.runtime.engine import VIS_GROUP
