@@ -27,10 +27,16 @@
                    context of every delivered row gathered on the device
                    (context_to_device, depth 8, lookback 65536);
                    --host-context builds it through the host instead (two
-                   queries per (agent, sender) pair, fetch, numpy, H2D)
+                   queries per (agent, sender) pair, fetch, numpy, H2D);
+                   --shared takes it with shared=True, the instantiation
+                   that checks visibility, over the same unrestricted log
+ 14 context-shared config 13's tick and pre-fill with 1/16 of each tick's
+                   messages sent as VIS_BITMAP broadcasts by a pair member,
+                   visible to the partner and three bystanders; the context
+                   is taken with shared=True and holds those broadcasts
 
 Usage:
-  python -m benchmarks.run --config {1,2,3,5,10,11,12,13} [--seconds S]
+  python -m benchmarks.run --config {1,2,3,5,10,11,12,13,14} [--seconds S]
   python -m torch.distributed.run --nproc-per-node N benchmarks/run.py --config 4
 
 Each config prints one JSON line:
@@ -52,9 +58,11 @@ sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
 
 from swarmdb_amd import MessagePriority, QueueConfig, SwarmsDB  # noqa: E402
 from swarmdb_amd.runtime.engine import (  # noqa: E402
+    BROADCAST,
     NO_BITMAP,
     REC_DTYPE,
     VIS_ALL,
+    VIS_BITMAP,
 )
 
 
@@ -468,7 +476,9 @@ def _host_context(eng, d, agents, depth: int, per_agent: int, host, ctx):
         dst[:t].copy_(src_t[:t])
 
 
-def config13_device_context(seconds: float, host_context: bool = False) -> None:
+def config13_device_context(seconds: float, host_context: bool = False,
+                            shared: bool = False,
+                            broadcasts: bool = False) -> None:
     """Config 10's tick (enqueue_batch -> receive_to_device -> ack_device,
     4096 x 1 KB) over a pre-filled log in which 64 agent pairs keep a
     running dialogue, plus the conversation context of every delivered row
@@ -477,7 +487,14 @@ def config13_device_context(seconds: float, host_context: bool = False) -> None:
     ``host_context`` through the host (two queries per distinct (agent,
     sender) pair, candidates gathered D2H, rows packed in numpy, H2D into
     the same layout). The last tick's context is compared with the CPU
-    double run over the same log."""
+    double run over the same log. ``shared`` takes the context with
+    shared=True. ``broadcasts`` is config 14: rounds 0, 17, 32 and 49 of
+    the 64 rounds of a tick (1/16 of its messages) are VIS_BITMAP
+    broadcasts by the pair member whose turn it is, visible to the partner
+    and to three bystanders (the sender's own bit is clear), so an agent
+    is delivered 30 messages of its partner and 8 broadcasts per tick and
+    the shared context of its rows holds its partner's and its own
+    broadcasts."""
     import torch  # before GpuEngine: torch's HIP runtime first
 
     from swarmdb_amd.runtime.engine import DeviceContext, Engine
@@ -501,6 +518,27 @@ def config13_device_context(seconds: float, host_context: bool = False) -> None:
     recs["sender"] = 2 * p + flip
     recs["receiver"] = 2 * p + 1 - flip
     agents = np.arange(na, dtype=np.uint32)
+    rows_per_tick = batch
+    if broadcasts:
+        if host_context:
+            raise ValueError("config 14 has no host route")
+        shared = True
+        bystanders = 3
+        handle = np.zeros(na, dtype=np.uint32)
+        for a in range(na):  # one bitmap per sender, made once
+            bits = np.zeros(cfg.max_agents, dtype=bool)
+            bits[a ^ 1] = True
+            bits[[(a + 2 * k) % na for k in range(1, bystanders + 1)]] = True
+            handle[a] = eng.alloc_bitmap(bits)
+        rnd = i // pairs
+        bc = (rnd % 32 == 0) | (rnd % 32 == 17)
+        recs["receiver"][bc] = BROADCAST
+        recs["vis_mode"][bc] = VIS_BITMAP
+        recs["bitmap"][bc] = handle[recs["sender"][bc]]
+        n_bc = int(bc.sum())
+        rows_per_tick = batch - n_bc + n_bc * (1 + bystanders)
+        per_agent = 48  # 30 from the partner, 8 broadcasts
+        assert rows_per_tick == na * 38
     state = {"d": None, "ctx": None}
     host = None
 
@@ -513,10 +551,10 @@ def config13_device_context(seconds: float, host_context: bool = False) -> None:
         elif context:
             state["ctx"] = eng.context_to_device(
                 d, agents, depth, lookback, max_payload=1024,
-                out=state["ctx"])
+                out=state["ctx"], shared=shared)
         eng.ack_device(d.seqs, n=d.total)
-        assert d.total == batch, "device tick failed to drain"
-        return d.total
+        assert d.total == rows_per_tick, "device tick failed to drain"
+        return batch
 
     for _ in range(lookback // batch):  # pre-fill: a lookback of dialogue
         tick(context=False)
@@ -545,17 +583,27 @@ def config13_device_context(seconds: float, host_context: bool = False) -> None:
     # (outside the timed region)
     got = state["ctx"].to_host()
     want = Engine.context_to_device(
-        eng, state["d"].to_host(), agents, depth, lookback, max_payload=1024)
+        eng, state["d"].to_host(), agents, depth, lookback, max_payload=1024,
+        shared=shared)
     want = want.to_host()
     assert (want.counts == depth).all(), "a row lacks its history"
     for name in ("counts", "seqs", "lengths", "headers", "payload"):
         a, b = getattr(got, name), getattr(want, name)
         assert np.array_equal(a, b), f"context {name} differs from the double"
+    extra = {"context": "host" if host_context else "device", "depth": depth,
+             "lookback": lookback, "pairs": pairs, "shared": shared}
+    if broadcasts:
+        slots = int((got.headers["receiver"] == BROADCAST).sum())
+        assert slots > 0, "no gathered slot is a broadcast"
+        extra.update(broadcasts_per_tick=n_bc, rows_per_tick=rows_per_tick,
+                     broadcast_slots=slots)
     eng.close()
+    if broadcasts:
+        _emit(14, "p2p-gpu-1kb-shared-context", n, elapsed,
+              float(np.median(lat) * 1000), extra)
+        return
     _emit(13, "p2p-gpu-1kb-device-context", n, elapsed,
-          float(np.median(lat) * 1000),
-          {"context": "host" if host_context else "device", "depth": depth,
-           "lookback": lookback, "pairs": pairs})
+          float(np.median(lat) * 1000), extra)
 
 
 def config3_group_fanout(seconds: float) -> None:
@@ -964,7 +1012,7 @@ def config5_loadbalancer(seconds: float) -> None:
 def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", type=int, required=True,
-                    choices=[1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13])
+                    choices=[1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14])
     ap.add_argument("--seconds", type=float, default=5.0)
     ap.add_argument("--host-return", action="store_true",
                     help="config 11: send the replies through the host")
@@ -972,6 +1020,8 @@ def main() -> int:
                     help="config 12: dispatch through the host")
     ap.add_argument("--host-context", action="store_true",
                     help="config 13: build the context through the host")
+    ap.add_argument("--shared", action="store_true",
+                    help="config 13: take the context with shared=True")
     args = ap.parse_args()
     if args.config == 1:
         config1_cpu_loopback(args.seconds)
@@ -1009,7 +1059,10 @@ def main() -> int:
     elif args.config == 12:
         config12_device_dispatch(args.seconds, args.host_dispatch)
     elif args.config == 13:
-        config13_device_context(args.seconds, args.host_context)
+        config13_device_context(args.seconds, args.host_context,
+                                args.shared)
+    elif args.config == 14:
+        config13_device_context(args.seconds, broadcasts=True)
     return 0
 
 

@@ -14,6 +14,14 @@
 // the consumer, so they are values, never indices: agent_row is range-
 // checked before it picks the polled agent, the sender is compared but
 // never dereferenced, the seq is clamped into [0, count].
+//
+// SHARED (context_to_device(..., shared=True)) widens the pair rule to
+// what one party wrote and the other was allowed to see: broadcasts
+// count, and a VIS_BITMAP / VIS_GROUP record is judged as k_receive
+// judges it for the OTHER party (never the author): no bitmap -> visible,
+// except a VIS_GROUP broadcast, which k_fanout hands to nobody; a pool
+// slot whose epoch moved on -> hidden; else that party's bit. Only log
+// records are consulted, never the delivered row's own bitmap fields.
 
 // Rows of a delivery one workgroup of k_context_find takes (CONTEXT_GROUP
 // / 4 per wavefront). 4 — one row per wavefront — measured best on a
@@ -24,6 +32,17 @@ constexpr int CONTEXT_GROUP = 4;
 constexpr int CONTEXT_GROUP_WIDE = 16;
 constexpr int CONTEXT_TILE = 256;     // seqs per tile: one per thread
 constexpr int CONTEXT_MAX_DEPTH = 64; // one lane per slot
+
+// SHARED only: 1 loads the record's last 16 B (byte 32: payload_len,
+// bitmap, content_len, bitmap_epoch) with the first, for every entry, so
+// that it flies with the next tile's loads; 0 loads it at decode time,
+// for a restricted candidate only. 0 measured 3 us faster on a 4096-row call
+// over a log with 1/16 restricted broadcasts (139 against 142 us) and the
+// same with none (profiles/device_context_shared.md), so it is the
+// default.
+#ifndef SWARMQ_CONTEXT_EAGER_VIS
+#define SWARMQ_CONTEXT_EAGER_VIS 0
+#endif
 
 // Step 1: which seqs. The workgroup walks the union window of its G rows
 // from newest to oldest in tiles of 256 seqs. Thread t loads the first
@@ -37,7 +56,14 @@ constexpr int CONTEXT_MAX_DEPTH = 64; // one lane per slot
 // rows times. The next tile's loads are issued before the current one is
 // tested. Every branch around a barrier depends on block-uniform values
 // only (top, wlo and the block-wide vote).
-template <int G>
+//
+// SHARED: the thread that stages an entry also settles what does not
+// depend on the row: it leaves in t_vis NO_BITMAP ("visible to all") or
+// the live pool slot, and clears the candidate bit of an entry nobody can
+// see. A lane that matches a restricted entry then loads the one bitmap
+// word that holds the other party's bit, before the ballot. With SHARED
+// false none of this is compiled and the bitmap pointers are not read.
+template <int G, bool SHARED>
 __global__ void __launch_bounds__(256)
     k_context_find(const long long *__restrict__ d_seqs,
                    const int *__restrict__ d_agent_row,
@@ -47,12 +73,15 @@ __global__ void __launch_bounds__(256)
                    u64 evict_base, u64 count, const Rec *__restrict__ hdr,
                    const u32 *__restrict__ status, int *__restrict__ out_counts,
                    long long *__restrict__ out_seqs,
-                   int *__restrict__ out_lengths, QueueGeom g) {
+                   int *__restrict__ out_lengths, QueueGeom g,
+                   const u64 *__restrict__ bitmaps,
+                   const u32 *__restrict__ bitmap_epochs) {
   static_assert(G % 4 == 0 && G >= 4, "G/4 rows per wavefront");
   constexpr int RPW = G / 4;
   __shared__ u32 t_sender[CONTEXT_TILE];
   __shared__ u32 t_receiver[CONTEXT_TILE];
   __shared__ u32 t_ok_type[CONTEXT_TILE]; // bit 8: candidate; bits 0..7: type
+  __shared__ u32 t_vis[SHARED ? CONTEXT_TILE : 1]; // NO_BITMAP or pool slot
   __shared__ u32 r_a[G], r_s[G];
   __shared__ long long r_lo[G], r_hi[G]; // lo >= hi: the row takes nothing
   __shared__ long long found[G][CONTEXT_MAX_DEPTH]; // newest first
@@ -113,9 +142,16 @@ __global__ void __launch_bounds__(256)
   // flight). One 64-bit modulo per tile; a loaded thread has tid <
   // t_top - tlo <= whi - evict_base <= num_slots, so one conditional
   // step wraps its slot. An entry outside the tile reads as DELETED.
-  auto load_tile = [&](long long t_top, uint4 &v, u32 &st) {
+  // SHARED: `at` is the entry's record, `w` its last 16 B when loaded
+  // here.
+  auto load_tile = [&](long long t_top, uint4 &v, u32 &st, const Rec *&at,
+                       uint4 &w) {
     v = make_uint4(0u, 0u, 0u, 0u);
     st = ST_DELETED;
+    if constexpr (SHARED) {
+      at = hdr;
+      w = make_uint4(0u, 0u, 0u, 0u);
+    }
     if (t_top <= wlo)
       return;
     const long long tlo =
@@ -127,24 +163,46 @@ __global__ void __launch_bounds__(256)
       slot -= g.num_slots;
     v = *reinterpret_cast<const uint4 *>(hdr + slot);
     st = status[slot];
+    if constexpr (SHARED) {
+      at = hdr + slot;
+      if (SWARMQ_CONTEXT_EAGER_VIS)
+        w = reinterpret_cast<const uint4 *>(at)[2];
+    }
   };
 
   long long top = whi; // exclusive end of the next tile; whi == 0: no window
-  uint4 v;
+  uint4 v, w;
   u32 st;
-  load_tile(top, v, st);
+  const Rec *at;
+  load_tile(top, v, st, at, w);
   while (top > wlo) {
     const long long tlo = top - CONTEXT_TILE > wlo ? top - CONTEXT_TILE : wlo;
     const u32 type = v.z & 0xFFu;
     const u32 vis = (v.z >> 16) & 0xFFu;
-    const bool ok = st != ST_DELETED && st != ST_FAILED && vis == VIS_ALL &&
-                    (type_code < 0 || type == (u32)type_code);
+    bool ok = st != ST_DELETED && st != ST_FAILED &&
+              (SHARED || vis == VIS_ALL) &&
+              (type_code < 0 || type == (u32)type_code);
+    if constexpr (SHARED) {
+      u32 pool = NO_BITMAP;
+      if (ok && (vis == VIS_BITMAP || vis == VIS_GROUP)) {
+        if (!SWARMQ_CONTEXT_EAGER_VIS)
+          w = reinterpret_cast<const uint4 *>(at)[2];
+        const u32 bm = w.y, epoch = w.w;
+        if (bm == NO_BITMAP)
+          ok = !(vis == VIS_GROUP && v.y == BROADCAST);
+        else if (bm >= g.num_bitmaps || bitmap_epochs[bm] != epoch)
+          ok = false; // recycled: hidden for good
+        else
+          pool = bm;
+      }
+      t_vis[tid] = pool;
+    }
     t_sender[tid] = v.x;
     t_receiver[tid] = v.y;
     t_ok_type[tid] = (ok ? 0x100u : 0u) | type;
     __syncthreads();
     // the next (older) tile's loads fly while this one is tested
-    load_tile(tlo, v, st);
+    load_tile(tlo, v, st, at, w);
 
     int open = 0; // a row of this wavefront may still take older seqs
 #pragma unroll
@@ -154,10 +212,27 @@ __global__ void __launch_bounds__(256)
           const int e = c * 64 + lane;
           const long long qe = tlo + e;
           const u32 es = t_sender[e], er = t_receiver[e];
-          const bool m = (t_ok_type[e] & 0x100u) && qe >= rlo[i] &&
-                         qe < rhi[i] && qe < top &&
-                         ((es == rs[i] && er == ra[i]) ||
-                          (es == ra[i] && er == rs[i]));
+          bool m = (t_ok_type[e] & 0x100u) && qe >= rlo[i] && qe < rhi[i] &&
+                   qe < top;
+          if constexpr (SHARED) {
+            // written by s for a to see, or by a for s to see
+            const bool to_a =
+                es == rs[i] && (er == ra[i] || er == BROADCAST);
+            const bool to_s =
+                es == ra[i] && (er == rs[i] || er == BROADCAST);
+            m = m && (to_a || to_s);
+            const u32 pool = t_vis[e];
+            if (m && pool != NO_BITMAP) {
+              const u32 other = to_a ? ra[i] : rs[i];
+              m = other < g.max_agents &&
+                  ((bitmaps[(u64)pool * g.bitmap_words + (other >> 6)] >>
+                    (other & 63)) &
+                   1ull);
+            }
+          } else {
+            m = m && ((es == rs[i] && er == ra[i]) ||
+                      (es == ra[i] && er == rs[i]));
+          }
           const ull mask = __ballot(m);
           if (mask) {
             // matches above this lane come first (newest first)

@@ -587,7 +587,8 @@ public:
   // [>= total, depth], headers [>= total, depth, 48] and payload
   // [>= total, depth, stride]. The polled agents are the only H2D and
   // nothing comes back. `type_code` < 0 means no filter; `group` picks
-  // the rows per workgroup (0: CONTEXT_GROUP). The window bounds are the
+  // the rows per workgroup (0: CONTEXT_GROUP); `shared` the instantiation
+  // that checks visibility against the bitmap pool. The window bounds are the
   // host-tracked count_ / evict_base_ every kernel of stream_ is launched
   // with. Reads queue state only; every check runs before anything is
   // launched; synchronizes.
@@ -597,7 +598,7 @@ public:
                          long long lookback, int type_code, u32 stride,
                          uintptr_t counts_ptr, uintptr_t ctx_seqs_ptr,
                          uintptr_t ctx_lengths_ptr, uintptr_t ctx_headers_ptr,
-                         uintptr_t ctx_payload_ptr, int group) {
+                         uintptr_t ctx_payload_ptr, int group, bool shared) {
     const int na = (int)agents.size();
     if (total < 0 || total > (1ll << 30) / CONTEXT_MAX_DEPTH)
       throw std::invalid_argument("context rows out of range");
@@ -624,8 +625,8 @@ public:
     py::gil_scoped_release nogil;
     upload_agents(agents.data(), na);
     const long long n_slots = total * depth;
-#define SWARMQ_CONTEXT_FIND(G)                                                 \
-  hipLaunchKernelGGL(k_context_find<G>,                                        \
+#define SWARMQ_CONTEXT_FIND(G, SHARED)                                         \
+  hipLaunchKernelGGL((k_context_find<G, SHARED>),                              \
                      dim3((unsigned)((total + (G) - 1) / (G))), dim3(256), 0,  \
                      stream_, reinterpret_cast<const long long *>(seqs_ptr),   \
                      reinterpret_cast<const int *>(agent_row_ptr),             \
@@ -634,11 +635,16 @@ public:
                      count_, d_hdr_, d_status_,                                \
                      reinterpret_cast<int *>(counts_ptr),                      \
                      reinterpret_cast<long long *>(ctx_seqs_ptr),              \
-                     reinterpret_cast<int *>(ctx_lengths_ptr), g_)
-    if (group == CONTEXT_GROUP_WIDE)
-      SWARMQ_CONTEXT_FIND(CONTEXT_GROUP_WIDE);
+                     reinterpret_cast<int *>(ctx_lengths_ptr), g_, d_bitmaps_, \
+                     d_bitmap_epochs_)
+    if (group == CONTEXT_GROUP_WIDE && shared)
+      SWARMQ_CONTEXT_FIND(CONTEXT_GROUP_WIDE, true);
+    else if (group == CONTEXT_GROUP_WIDE)
+      SWARMQ_CONTEXT_FIND(CONTEXT_GROUP_WIDE, false);
+    else if (shared)
+      SWARMQ_CONTEXT_FIND(CONTEXT_GROUP, true);
     else
-      SWARMQ_CONTEXT_FIND(CONTEXT_GROUP);
+      SWARMQ_CONTEXT_FIND(CONTEXT_GROUP, false);
 #undef SWARMQ_CONTEXT_FIND
     hipLaunchKernelGGL(k_context_gather, dim3((unsigned)((n_slots + 3) / 4)),
                        dim3(256), 0, stream_,

@@ -31,6 +31,7 @@ PYBIND11_MODULE(_swarmq, m) {
   m.attr("RECV_WINDOW") = RECV_WINDOW;
   m.attr("CONTEXT_GROUP") = CONTEXT_GROUP;
   m.attr("CONTEXT_GROUP_WIDE") = CONTEXT_GROUP_WIDE;
+  m.attr("CONTEXT_EAGER_VIS") = SWARMQ_CONTEXT_EAGER_VIS;
 
   m.def("device_count", []() {
     int n = 0;
@@ -87,7 +88,8 @@ PYBIND11_MODULE(_swarmq, m) {
            py::arg("depth"), py::arg("lookback"), py::arg("type_code"),
            py::arg("stride"), py::arg("counts_ptr"), py::arg("ctx_seqs_ptr"),
            py::arg("ctx_lengths_ptr"), py::arg("ctx_headers_ptr"),
-           py::arg("ctx_payload_ptr"), py::arg("group") = 0)
+           py::arg("ctx_payload_ptr"), py::arg("group") = 0,
+           py::arg("shared") = false)
       .def("fetch", &DeviceQueue::fetch)
       .def("fetch_raw", &DeviceQueue::fetch_raw, py::arg("seqs"),
            py::arg("stride") = 0, py::arg("synchronize") = true)

@@ -344,11 +344,12 @@ class CpuEngine(Engine):
         return self._hdr[lo:hi], self._status[lo:hi]
 
     def context_to_device(self, delivery, agent_idxs, depth, lookback,
-                          type_code=None, max_payload=0, out=None):
+                          type_code=None, max_payload=0, out=None, *,
+                          shared=False):
         with self._lock:
             return super().context_to_device(
                 delivery, agent_idxs, depth, lookback, type_code,
-                max_payload, out,
+                max_payload, out, shared=shared,
             )
 
     def peek_inbox(self, agent_idx: int) -> np.ndarray:

@@ -293,6 +293,13 @@ class DeviceContext:
 
     ``headers`` and ``payload`` of undefined slots, and everything at rows
     ``>= total``, are unspecified.
+
+    A gathered header is the log's record as stored. With ``shared=True``
+    a slot may hold a message of restricted visibility: on the GPU engine
+    its ``bitmap`` is the pool slot and its ``bitmap_epoch`` the
+    :meth:`Engine.alloc_bitmap` handle, on the CPU engine ``bitmap`` is
+    the index and ``bitmap_epoch`` is 0 — the two fields in which the
+    engines' contexts of the same traffic legitimately differ.
     """
 
     counts: Any
@@ -356,6 +363,15 @@ def check_context_args(
     if len(raw) and (raw.min() < 0 or raw.max() > 0xFFFFFFFF):
         raise ValueError("agent index out of range")
     return depth, lookback, code, np.ascontiguousarray(raw, dtype=np.uint32)
+
+
+def check_context_shared(shared: Any) -> bool:
+    """``shared`` of :meth:`Engine.context_to_device`: a ``bool`` and
+    nothing else (``1`` or ``"yes"`` is a ValueError — the flag picks
+    another rule, so a truthy accident must not)."""
+    if not isinstance(shared, (bool, np.bool_)):
+        raise ValueError("shared must be a bool")
+    return bool(shared)
 
 
 def check_context_out(
@@ -1027,6 +1043,50 @@ class Engine(abc.ABC):
         hdrs, _, _ = self.fetch_raw_chunks(np.arange(lo, hi, dtype=np.uint64))
         return hdrs, np.asarray(hdrs["status"])
 
+    def _context_visibility(
+        self, wh: np.ndarray, ok: np.ndarray
+    ) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """The part of ``sees`` that does not depend on the reader, for
+        the window records ``wh`` that are candidates (``ok``): ``ok``
+        without the records nobody can see, per record the row of its
+        live bitmap in ``bits`` (``-1``: visible to all), and ``bits``
+        (bool ``[k, max_agents]``, ``k >= 1``). Each distinct (bitmap,
+        epoch) is read once, through :meth:`read_bitmap`."""
+        max_agents = int(self.cfg.max_agents)  # type: ignore[attr-defined]
+        vis = wh["vis_mode"]
+        ok = ok.copy()
+        pool = np.full(len(wh), -1, dtype=np.int64)
+        rows: List[np.ndarray] = []
+        known: Dict[Tuple[int, int], int] = {}
+        restricted = ok & ((vis == VIS_BITMAP) | (vis == VIS_GROUP))
+        for i in np.flatnonzero(restricted).tolist():
+            bm = int(wh["bitmap"][i])
+            if bm == NO_BITMAP:
+                if vis[i] == VIS_GROUP and wh["receiver"][i] == BROADCAST:
+                    ok[i] = False  # fanned out to nobody
+                continue
+            key = (bm, int(wh["bitmap_epoch"][i]))
+            row = known.get(key)
+            if row is None:
+                try:
+                    b = self.read_bitmap(*key)
+                except IndexError:  # outside the pool
+                    b = None
+                row = -1
+                if b is not None:
+                    row = len(rows)
+                    full = np.zeros(max_agents, dtype=bool)
+                    b = np.asarray(b, dtype=bool)[:max_agents]
+                    full[:len(b)] = b
+                    rows.append(full)
+                known[key] = row
+            if row < 0:
+                ok[i] = False  # recycled: hidden for good
+            else:
+                pool[i] = row
+        bits = np.stack(rows) if rows else np.zeros((1, max_agents), bool)
+        return ok, pool, bits
+
     def context_to_device(
         self,
         delivery: DeviceDelivery,
@@ -1036,6 +1096,8 @@ class Engine(abc.ABC):
         type_code: Optional[int] = None,
         max_payload: int = 0,
         out: Optional[DeviceContext] = None,
+        *,
+        shared: bool = False,
     ) -> DeviceContext:
         """Gather the conversation context of every row of ``delivery``
         (polled with ``agent_idxs``) from the log into engine-resident
@@ -1067,15 +1129,60 @@ class Engine(abc.ABC):
         stride as in :meth:`receive_to_device`. Only queue state is read:
         no cursor, status, counter or load changes.
 
+        With ``shared=True`` (keyword-only, opt-in) the context of a row
+        holds the newest messages one of the two parties wrote and the
+        other party was allowed to see: broadcasts and group messages are
+        included, and visibility is checked exactly as delivery checks
+        it. ``a``, ``s``, ``lo``, ``hi``, ``depth`` and the slot order
+        are as above; only ``match`` changes::
+
+            sees(x, q) := what a poll by agent x does with q once q is in
+                          x's inbox (k_receive):
+              vis_mode(q) not in {VIS_BITMAP, VIS_GROUP}  -> True
+              bitmap(q) == NO_BITMAP        -> True, except for a VIS_GROUP
+                                               broadcast (receiver ==
+                                               BROADCAST): k_fanout gives it
+                                               to no inbox -> False
+              bitmap(q) >= num_bitmaps      -> False
+              the pool slot's epoch != bitmap_epoch(q)
+                                            -> False  (recycled: hidden
+                                                       for good)
+              otherwise                     -> bit x of that bitmap
+
+            match(q) := status(q) not in {DELETED, FAILED}
+                    and (type_code is None or hdr(q).type == type_code)
+                    and (   (hdr(q).sender == s
+                             and hdr(q).receiver in {a, BROADCAST}
+                             and sees(a, q))
+                         or (hdr(q).sender == a
+                             and hdr(q).receiver in {s, BROADCAST}
+                             and sees(s, q)))
+
+        The bit tested is always the other party's, never the author's (a
+        facade broadcast leaves the sender's own bit clear, and that does
+        not matter); with ``a == s`` the two lines say the same thing.
+        Whether an agent was registered when a broadcast was sent cannot
+        be recovered from the log and is not considered: a broadcast one
+        party sent before the other registered still appears. An ``a``
+        that is no agent index (``>= max_agents``) has no bit and sees
+        nothing restricted. The delivered row's own ``bitmap`` fields are
+        never used, only log records are. With ``shared=False`` every
+        call behaves as it always did.
+
         Every refusal (``depth`` outside ``1..64``, ``lookback`` outside
         ``1..2**31-1``, a ``type_code`` outside one byte, an
         ``agent_idxs`` of another length than the delivery's or longer
-        than ``max_agents``, unusable delivery arrays, an ``out`` built
-        for another ``depth`` or stride or with too few rows) is a
-        ValueError raised before anything is gathered.
+        than ``max_agents``, a ``shared`` that is not a ``bool``, unusable
+        delivery arrays, an ``out`` built for another ``depth`` or stride
+        or with too few rows) is a ValueError raised before anything is
+        gathered.
 
-        Default: the CPU double, plain numpy over the log window."""
+        Default: the CPU double, plain numpy over the log window (bitmaps
+        through :meth:`read_bitmap`, where ``None`` — recycled — means
+        hidden); ``Engine.context_to_device(gpu_engine, delivery.to_host(),
+        ...)`` runs it over a GPU engine's own log."""
         cfg = self.cfg  # type: ignore[attr-defined]
+        shared = check_context_shared(shared)
         total = int(delivery.total)
         depth, lookback, code, agents = check_context_args(
             depth, lookback, type_code, agent_idxs, len(delivery.counts),
@@ -1140,17 +1247,27 @@ class Engine(abc.ABC):
             # (agent, sender) pair, ascending, serve all its rows
             wlo, whi = int(lo[live].min()), int(hi[live].max())
             wh, wst = self._context_window(wlo, whi)
-            ok = (wst != ST_DELETED) & (wst != ST_FAILED) \
-                & (wh["vis_mode"] == VIS_ALL)
+            ok = (wst != ST_DELETED) & (wst != ST_FAILED)
             if code >= 0:
                 ok &= wh["type"] == code
             snd = wh["sender"].astype(np.int64)
             rcv = wh["receiver"].astype(np.int64)
+            if shared:
+                ok, pool, bits = self._context_visibility(wh, ok)
+            else:
+                ok &= wh["vis_mode"] == VIS_ALL
             matches: Dict[Tuple[int, int], np.ndarray] = {}
             for r in np.flatnonzero(live).tolist():
                 a, s = int(a_of[r]), int(s_of[r])
                 m = matches.get((a, s))
-                if m is None:
+                if m is None and shared:
+                    to_a = (snd == s) & ((rcv == a) | (rcv == BROADCAST))
+                    to_s = (snd == a) & ((rcv == s) | (rcv == BROADCAST))
+                    free = pool < 0
+                    sees_a = free | bits[pool, a] if a < bits.shape[1] else free
+                    pair = (to_a & sees_a) | (to_s & (free | bits[pool, s]))
+                    m = matches[(a, s)] = np.flatnonzero(ok & pair) + wlo
+                elif m is None:
                     pair = ((snd == s) & (rcv == a)) | ((snd == a) & (rcv == s))
                     m = matches[(a, s)] = np.flatnonzero(ok & pair) + wlo
                 i0 = int(np.searchsorted(m, lo[r]))

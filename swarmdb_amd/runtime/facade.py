@@ -791,6 +791,8 @@ class SwarmsDB:
         message_type: Union[MessageType, str, None] = None,
         max_payload: int = 0,
         out: Optional[DeviceContext] = None,
+        *,
+        shared: bool = False,
     ) -> DeviceContext:
         """The conversation context of every row of a
         :meth:`receive_device` delivery, gathered without leaving the
@@ -799,8 +801,17 @@ class SwarmsDB:
         messages, oldest first, that the polled agent and the row's sender
         exchanged among the ``lookback`` messages logged before the row's
         own (see :meth:`Engine.context_to_device` for the rules and
-        :class:`DeviceContext` for the tensors). Broadcasts and messages
-        with restricted visibility never appear; with ``message_type``
+        :class:`DeviceContext` for the tensors). With the default
+        ``shared=False`` only unrestricted point-to-point messages
+        appear: broadcasts and messages with restricted visibility never
+        do, which leaves out everything :meth:`broadcast_message`,
+        :meth:`send_to_group_fast` and ``send_message(visible_to=...)``
+        send. With ``shared=True`` the context holds what one of the two
+        wrote and the other was allowed to see: the point-to-point
+        messages between them, and each one's broadcasts and group
+        messages whose visibility — checked as delivery checks it —
+        includes the other. Messages by third parties never appear in
+        either mode. With ``message_type``
         only messages of that type do. ``agent_ids`` is the list the
         delivery was polled with; unregistered ids, or a list of another
         length than the delivery's, raise ValueError. Nothing in the queue
@@ -819,7 +830,8 @@ class SwarmsDB:
         code = None if message_type is None else _type_code(message_type)
         with tracer.span("context_device", n=int(delivery.total)):
             return self.engine.context_to_device(
-                delivery, idxs, depth, lookback, code, max_payload, out
+                delivery, idxs, depth, lookback, code, max_payload, out,
+                shared=shared,
             )
 
     def messages_from_context(
@@ -829,7 +841,9 @@ class SwarmsDB:
         oldest first — the debugging / parity bridge of
         :meth:`context_device`, as :meth:`messages_from_delivery` is of
         :meth:`receive_device` (a host copy plus per-message Python work;
-        not a hot path)."""
+        not a hot path). A context taken with ``shared=True`` may hold
+        restricted messages; their ``visible_to`` decodes as it does for
+        :meth:`messages_from_delivery`."""
         h = ctx.to_host()
         if not 0 <= int(row) < h.total:
             raise ValueError("row must be within the context's rows")

@@ -31,6 +31,7 @@ from .engine import (
     Engine,
     check_context_args,
     check_context_out,
+    check_context_shared,
     check_delivery_out,
     check_dispatch_args,
     check_dispatch_out,
@@ -813,6 +814,8 @@ class GpuEngine(Engine):
         max_payload: int = 0,
         out: Optional[DeviceContext] = None,
         group: int = 0,
+        *,
+        shared: bool = False,
     ) -> DeviceContext:
         """k_context_find + k_context_gather over the delivery's own
         tensors and the HBM-resident log (see
@@ -821,10 +824,14 @@ class GpuEngine(Engine):
         device and no byte comes back. ``group`` picks the delivery rows
         one workgroup shares a log pass among (0: the built default,
         ``_swarmq.CONTEXT_GROUP``, one row per wavefront; 16: four, for
-        measurement). The caller's current torch stream is drained first
+        measurement). ``shared`` picks the instantiation that checks
+        visibility against the bitmap pool and its epochs in the kernel;
+        with the default ``False`` the kernel that runs is the one that
+        always ran. The caller's current torch stream is drained first
         (the delivery's tensors may still be being written) and the
         engine's stream is synchronized before return."""
         torch, dev = self._torch_device()
+        shared = check_context_shared(shared)
         total = int(delivery.total)
         depth, lookback, code, agents = check_context_args(
             depth, lookback, type_code, agent_idxs, len(delivery.counts),
@@ -865,7 +872,7 @@ class GpuEngine(Engine):
                     delivery.headers.data_ptr(), total, agents, D, lookback,
                     code, stride, counts.data_ptr(), seqs.data_ptr(),
                     lengths.data_ptr(), headers.data_ptr(),
-                    payload.data_ptr(), int(group),
+                    payload.data_ptr(), int(group), shared,
                 )
         return DeviceContext(
             counts=counts, seqs=seqs, lengths=lengths, headers=headers,
