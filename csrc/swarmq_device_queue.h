@@ -764,16 +764,22 @@ public:
   }
 
   // Filter scan over [lo, hi); returns matched seqs (unordered).
+  // `max_blocks` > 0 caps the grid (a test's way into the grid-stride
+  // loop at a small size); 0 is the production cap.
   py::array_t<u64> query_range(u64 lo, u64 hi, int f_sender, int f_receiver,
                                int f_type, int f_status, double after,
-                               double before, u32 pred_mask, u32 cap) {
+                               double before, u32 pred_mask, u32 cap,
+                               int max_blocks) {
+    if (max_blocks < 0)
+      throw std::invalid_argument("blocks must be >= 0");
     if (!clamp_scan(lo, hi, cap))
       return py::array_t<u64>(0);
     {
       py::gil_scoped_release nogil;
       HIP_CHECK(hipMemsetAsync(d_match_count_, 0, sizeof(u32), stream_));
       const u64 span = hi - lo;
-      const int blocks = (int)std::min<u64>((span + 255) / 256, 2048); // grid-stride
+      const int blocks = (int)std::min<u64>(
+          (span + 255) / 256, max_blocks ? max_blocks : 2048); // grid-stride
       hipLaunchKernelGGL(k_filter, dim3(blocks), dim3(256), 0, stream_, lo, hi,
                          f_sender, f_receiver, f_type, f_status, after, before,
                          pred_mask, d_hdr_, d_status_, d_match_,
@@ -782,11 +788,22 @@ public:
     return read_matches(cap);
   }
 
+  // Substring scan over [lo, hi); returns matched seqs (unordered, a seq
+  // possibly once per matching chunk). `max_blocks` > 0 caps each
+  // segment's grid and `loads` in {2,4,8} picks k_search<loads> (a test's
+  // way into the pipelined loop and the other instantiations at a small
+  // size); 0 is the production choice: SWARMQ_SEARCH_BLOCKS /
+  // SWARMQ_SEARCH_P where they hold a usable value, else the measured
+  // defaults.
   py::array_t<u64> search_range(u64 lo, u64 hi, py::bytes needle, bool fold,
-                                u32 cap) {
+                                u32 cap, int max_blocks, int loads) {
     std::string nd = needle;
     if (nd.empty() || nd.size() > 256)
       throw std::invalid_argument("needle must be 1..256 bytes");
+    if (max_blocks < 0)
+      throw std::invalid_argument("blocks must be >= 0");
+    if (loads != 0 && loads != 2 && loads != 4 && loads != 8)
+      throw std::invalid_argument("loads must be 0, 2, 4 or 8");
     if (!clamp_scan(lo, hi, cap))
       return py::array_t<u64>(0);
     {
@@ -798,10 +815,19 @@ public:
       // ranges (ring wraps once): launch a pure linear-scan kernel per
       // segment. Grid size A/B'd on hardware (see profiles/ and
       // csrc/bench_membw.hip).
-      static const int sblocks = [] {
-        const char *e = getenv("SWARMQ_SEARCH_BLOCKS");
-        return e ? atoi(e) : 16384;
+      // an env value that is no positive block count (or no load count
+      // of a compiled kernel) never reaches the launch: a zero-block
+      // grid is a launch error
+      static const int env_blocks = [] {
+        const long v = env_long("SWARMQ_SEARCH_BLOCKS");
+        return v > 0 && v <= INT_MAX ? (int)v : 16384;
       }();
+      static const int env_loads = [] {
+        const long v = env_long("SWARMQ_SEARCH_P");
+        return v == 4 || v == 8 ? (int)v : 2; // hardware A/B winner (profiles/)
+      }();
+      const int sblocks = max_blocks ? max_blocks : env_blocks;
+      const int sP = loads ? loads : env_loads;
       const u32 cps = g_.slot_bytes >> 4;
       const u64 span = hi - lo;
       const u32 slot_lo = (u32)(lo % g_.num_slots);
@@ -817,10 +843,6 @@ public:
         const u64 chunks = s.nslots * cps;
         const int blocks =
             (int)std::min<u64>((chunks + 255) / 256, sblocks);
-        static const int sP = [] {
-          const char *e = getenv("SWARMQ_SEARCH_P");
-          return e ? atoi(e) : 2; // hardware A/B winner (profiles/)
-        }();
         auto kfn = k_search<2>;
         if (sP == 4)
           kfn = k_search<4>;
@@ -1344,6 +1366,17 @@ private:
     hi = std::min(hi, count_);
     cap = std::min(cap, staging_batch_);
     return lo < hi;
+  }
+
+  // An environment variable that is one whole decimal integer, else 0.
+  static long env_long(const char *name) {
+    const char *e = getenv(name);
+    if (!e || !*e)
+      return 0;
+    char *end = nullptr;
+    errno = 0;
+    const long v = strtol(e, &end, 10);
+    return (errno || *end) ? 0 : v;
   }
 
   // The matches a scan on stream_ left in d_match_ (at most `cap`).

@@ -73,6 +73,10 @@ __global__ void k_enqueue_meta(const Rec *__restrict__ stage, int n,
       status[slot] = ST_FAILED;
       atomicAdd(&h_failed, 1u);
     } else {
+      // the search window is a prefix of the payload: a content_len the
+      // host never saw must not reach past the bytes this record wrote
+      // (into the slot's previous occupant, or the next slot)
+      h.content_len = min(h.content_len, h.payload_len);
       hdr[slot] = h;
       status[slot] = ST_DELIVERED;
       atomicAdd(&h_type[r.type], 1u);

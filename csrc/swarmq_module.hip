@@ -98,8 +98,14 @@ PYBIND11_MODULE(_swarmq, m) {
       .def("set_statuses", &DeviceQueue::set_statuses)
       .def("get_status", &DeviceQueue::get_status)
       .def("get_statuses", &DeviceQueue::get_statuses)
-      .def("query_range", &DeviceQueue::query_range)
-      .def("search_range", &DeviceQueue::search_range)
+      .def("query_range", &DeviceQueue::query_range, py::arg("lo"),
+           py::arg("hi"), py::arg("sender"), py::arg("receiver"),
+           py::arg("type_code"), py::arg("status"), py::arg("after"),
+           py::arg("before"), py::arg("pred_mask"), py::arg("cap"),
+           py::arg("blocks") = 0)
+      .def("search_range", &DeviceQueue::search_range, py::arg("lo"),
+           py::arg("hi"), py::arg("needle"), py::arg("fold"), py::arg("cap"),
+           py::arg("blocks") = 0, py::arg("loads") = 0)
       .def("inbox_window", &DeviceQueue::inbox_window)
       .def("unread_counts", &DeviceQueue::unread_counts)
       .def("counters", &DeviceQueue::counters)

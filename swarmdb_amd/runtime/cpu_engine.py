@@ -164,6 +164,11 @@ class CpuEngine(Engine):
             )
             good = ~bad
             self._hdr[sl] = recs
+            # the search window is a prefix of the payload (k_enqueue_meta's
+            # clamp); the error lane stores no window at all
+            self._hdr["content_len"][sl] = np.where(
+                good, np.minimum(recs["content_len"], recs["payload_len"]), 0
+            )
             heap_base = len(self._heap)
             self._heap += payloads
             self._pay_off[sl] = recs["payload_off"] + np.uint64(heap_base)
@@ -312,9 +317,10 @@ class CpuEngine(Engine):
 
     def _park_failed(self, seqs: np.ndarray) -> np.ndarray:
         # the stored header of an error-lane record, as k_enqueue_meta
-        # leaves it: no payload. enqueue_batch keeps the caller's lengths
-        # in the header (only the heap length is zeroed), which for a
-        # device-side record would be the OVERSIZE_LEN marker
+        # leaves it: no payload. enqueue_batch keeps the caller's
+        # payload_len in the header (only the heap length and the content
+        # window are zeroed), which for a device-side record would be the
+        # OVERSIZE_LEN marker
         if len(seqs):
             idx = seqs.astype(np.int64)
             failed = idx[self._status[idx] == ST_FAILED]

@@ -78,7 +78,8 @@ FLAG_OVERFLOW = 8     # payload exceeds the slot capacity and lives in the
 # per-message batch record (host staging). 48 bytes, 8-byte aligned.
 # Payload layout: [content bytes (content_len)][extras JSON (rest)] —
 # search scans only the content window (reference searches the content
-# field only, swarmdb/ main.py:742-781).
+# field only, swarmdb/ main.py:742-781). Enqueue stores content_len =
+# min(content_len, payload_len): see Engine's docstring.
 REC_DTYPE = np.dtype(
     {
         "names": [
@@ -505,7 +506,16 @@ def check_reply_fields(
 class Engine(abc.ABC):
     """Abstract delivery engine. All indices are dense agent indices
     assigned by :meth:`register_agent`; the facade maps agent-id strings
-    to indices."""
+    to indices.
+
+    A message's payload is ``[content (content_len)][extras JSON (rest)]``
+    and :meth:`search` scans ``payload[:content_len]`` only. Every enqueue
+    path — host batch, staged and graph ticks, device send and replies,
+    router ingest, checkpoint load — stores ``content_len =
+    min(content_len, payload_len)`` for a good record and 0 for an
+    error-lane one, so the window never reaches past the bytes the record
+    itself wrote: not into what the slot's previous occupant left behind,
+    not into the next slot. :meth:`fetch` returns the stored value."""
 
     # --- registry ---
 

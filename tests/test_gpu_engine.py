@@ -200,6 +200,18 @@ def test_parity_cpu_vs_gpu():
         cpu.delete(8)
         assert gpu.get_status(8) == cpu.get_status(8) == ST_DELETED
         assert (gpu.query(limit=total) == cpu.query(limit=total)).all()
+
+        # search parity: folded, exact, and a needle that is absent
+        # (tests/test_scan_kernels.py holds the search kernel's own suite)
+        sg = gpu.search(b"qu", case_sensitive=False, limit=total)
+        sc = cpu.search(b"qu", case_sensitive=False, limit=total)
+        assert len(sc) > 0 and sg.tolist() == sc.tolist()
+        sg = gpu.search(b"Qu", case_sensitive=True, limit=total)
+        sc = cpu.search(b"Qu", case_sensitive=True, limit=total)
+        assert 0 < len(sc) < len(gpu.search(b"qu", False, total))
+        assert sg.tolist() == sc.tolist()
+        assert len(gpu.search(b"\x01absent\x02", False, total)) == 0
+        assert len(cpu.search(b"\x01absent\x02", False, total)) == 0
     finally:
         gpu.close()
 
