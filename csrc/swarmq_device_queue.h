@@ -186,6 +186,7 @@ public:
   // waited on the stream before the launch).
   void build_tick(int n, py::array_t<u32> agents, int K, bool priority) {
     const int na = (int)agents.size();
+    check_polled(agents, K, true);
     if (n <= 0 || (u32)n > staging_batch_)
       throw std::invalid_argument("bad tick batch size");
     if ((size_t)na * K > out_pool_)
@@ -343,8 +344,7 @@ public:
     if (total < 0 || (u32)total > staging_batch_)
       throw std::invalid_argument("batch exceeds staging_batch");
     check_row_stride(rstride);
-    if ((u32)na > g_.max_agents)
-      throw std::invalid_argument("more polled agents than max_agents");
+    check_polled(agents, 0, false);
     if (priority > 255 || type_code > 255u || flags > 255u)
       throw std::invalid_argument("type, priority and flags are one byte");
     if (total == 0)
@@ -434,6 +434,7 @@ public:
   py::tuple receive_many(py::array_t<u32> agents, int max_per_agent,
                          bool priority, bool return_seqs = true) {
     const int na = (int)agents.size();
+    check_polled(agents, max_per_agent, true);
     if (na == 0)
       return py::make_tuple(py::array_t<u32>(0), py::array_t<u64>(0));
     if ((size_t)na * max_per_agent > out_pool_)
@@ -507,10 +508,7 @@ public:
                                      uintptr_t offsets_ptr,
                                      size_t capacity_rows) {
     const int na = (int)agents.size();
-    if (max_per_agent < 0)
-      throw std::invalid_argument("max_per_agent must be >= 0");
-    if ((u32)na > g_.max_agents)
-      throw std::invalid_argument("more polled agents than max_agents");
+    check_polled(agents, max_per_agent, true);
     const size_t rows = (size_t)na * (size_t)max_per_agent;
     if (rows > out_pool_)
       throw std::invalid_argument("receive batch exceeds output pool");
@@ -525,9 +523,6 @@ public:
                    rows != 0, "delivery buffer pointer is null",
                    "delivery buffer is misaligned");
     const u32 *ap = agents.data();
-    for (int i = 0; i < na; ++i)
-      if (ap[i] >= g_.max_agents)
-        throw std::invalid_argument("agent index out of range");
     py::array_t<u32> counts(na);
     if (na == 0)
       return counts;
@@ -608,8 +603,7 @@ public:
       throw std::invalid_argument("lookback must be within 1..2^31-1");
     if (type_code > 255)
       throw std::invalid_argument("type is one byte");
-    if ((u32)na > g_.max_agents)
-      throw std::invalid_argument("more polled agents than max_agents");
+    check_polled(agents, 0, false);
     check_row_stride(stride);
     if (group == 0)
       group = CONTEXT_GROUP;
@@ -720,8 +714,8 @@ public:
       HIP_CHECK(hipMemcpyAsync(d_seqs_in_, seqs.data(), n * sizeof(u64),
                                hipMemcpyHostToDevice, copy_stream_));
       hipLaunchKernelGGL(k_statuses, dim3((n + 255) / 256), dim3(256), 0,
-                         copy_stream_, d_seqs_in_, n, evict_base_, d_status_,
-                         d_fetch_status_, g_);
+                         copy_stream_, d_seqs_in_, n, evict_base_, count_,
+                         d_status_, d_fetch_status_, g_);
       HIP_CHECK(hipMemcpyAsync(h_fetch_status_, d_fetch_status_,
                                n * sizeof(u32), hipMemcpyDeviceToHost,
                                copy_stream_));
@@ -743,14 +737,14 @@ public:
     HIP_CHECK(hipMemcpyAsync(d_choices_, sts.data(), n * sizeof(u32),
                              hipMemcpyHostToDevice, stream_));
     hipLaunchKernelGGL(k_set_statuses, dim3((n + 255) / 256), dim3(256), 0,
-                       stream_, d_seqs_in_, d_choices_, n, d_status_,
-                       d_by_status_, g_);
+                       stream_, d_seqs_in_, d_choices_, n, evict_base_, count_,
+                       d_status_, d_by_status_, g_);
     HIP_CHECK(hipStreamSynchronize(stream_));
   }
 
   void set_status(u64 seq, u32 st) {
     hipLaunchKernelGGL(k_set_status, dim3(1), dim3(64), 0, stream_, seq, st,
-                       d_status_, d_by_status_, g_);
+                       evict_base_, count_, d_status_, d_by_status_, g_);
     HIP_CHECK(hipStreamSynchronize(stream_));
   }
 
@@ -885,6 +879,7 @@ public:
 
   py::array_t<u32> unread_counts(py::array_t<u32> agents) {
     const int na = (int)agents.size();
+    check_polled(agents, 0, false);
     py::array_t<u32> out(na);
     if (na == 0)
       return out;
@@ -1217,6 +1212,35 @@ private:
       throw std::out_of_range("agent index out of range");
   }
 
+  // The polled-agent list of a call, checked before it goes to d_agents_
+  // (max_agents words) and before anything is launched: no longer than
+  // max_agents, every index below it, max_per_agent >= 0 and, for a
+  // dequeue (`unique`), no agent twice: two workgroups of k_receive on one
+  // agent would race on its cursor, carry buffer and counter. Calls that
+  // only read through the list pass unique = false.
+  void check_polled(const py::array_t<u32> &agents, int max_per_agent,
+                    bool unique) {
+    if (max_per_agent < 0)
+      throw std::invalid_argument("max_per_agent must be >= 0");
+    const size_t na = (size_t)agents.size();
+    if (na > g_.max_agents)
+      throw std::invalid_argument("more polled agents than max_agents");
+    const u32 *ap = agents.data();
+    for (size_t i = 0; i < na; ++i)
+      if (ap[i] >= g_.max_agents)
+        throw std::invalid_argument("agent index out of range");
+    if (!unique)
+      return;
+    polled_seen_.assign(g_.bitmap_words, 0);
+    for (size_t i = 0; i < na; ++i) {
+      u64 &w = polled_seen_[ap[i] >> 6];
+      const u64 bit = 1ull << (ap[i] & 63);
+      if (w & bit)
+        throw std::invalid_argument("agent polled twice in one call");
+      w |= bit;
+    }
+  }
+
   static bool bad_slot(int slot) { return slot < 0 || slot > 1; }
 
   static void check_slot(int slot) {
@@ -1475,6 +1499,7 @@ private:
   int last_recv_na_ = 0;
   int last_recv_K_ = 0;
   u32 bitmap_next_ = 0;
+  std::vector<u64> polled_seen_; // check_polled's max_agents-bit scratch
   bool released_ = false;
   size_t out_pool_ = 0;
   size_t stage_pay_bytes_ = 0;

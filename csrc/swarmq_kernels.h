@@ -650,34 +650,46 @@ __global__ void k_unread(const u32 *__restrict__ agents, int n_agents,
     out[b] = cnt;
 }
 
-// Batched status gather (no payload traffic).
+// Batched status gather (no payload traffic). A seq outside the live
+// window [evict_base, count) reads DELETED, as get_status has it: its
+// slot holds another message, or none yet.
 __global__ void k_statuses(const u64 *__restrict__ seqs, int n,
-                           u64 evict_base, const u32 *__restrict__ status,
+                           u64 evict_base, u64 count,
+                           const u32 *__restrict__ status,
                            u32 *__restrict__ out, QueueGeom g) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n)
     return;
   const u64 s = seqs[i];
-  out[i] = (s < evict_base) ? ST_DELETED : status[s % g.num_slots];
+  out[i] = (s < evict_base || s >= count) ? ST_DELETED
+                                          : status[s % g.num_slots];
 }
 
 // Batched status mutation with counter upkeep (history load restore).
+// An evicted seq is skipped (its slot belongs to a newer message), so is
+// one never assigned, as in k_ack_device; a tombstone IS overwritten.
 __global__ void k_set_statuses(const u64 *__restrict__ seqs,
                                const u32 *__restrict__ new_status, int n,
+                               u64 evict_base, u64 count,
                                u32 *__restrict__ status,
                                ull *__restrict__ by_status, QueueGeom g) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n)
     return;
-  const u32 slot = (u32)(seqs[i] % g.num_slots);
-  swap_status(status, by_status, slot, new_status[i]);
+  const u64 s = seqs[i];
+  if (s < evict_base || s >= count)
+    return;
+  swap_status(status, by_status, (u32)(s % g.num_slots), new_status[i]);
 }
 
 // Status mutation with counter upkeep (mark processed / admin status
-// updates / delete tombstones).
-__global__ void k_set_status(u64 seq, u32 new_status, u32 *__restrict__ status,
+// updates / delete tombstones). Same skip rule as k_set_statuses.
+__global__ void k_set_status(u64 seq, u32 new_status, u64 evict_base,
+                             u64 count, u32 *__restrict__ status,
                              ull *__restrict__ by_status, QueueGeom g) {
   if (threadIdx.x == 0 && blockIdx.x == 0) {
+    if (seq < evict_base || seq >= count)
+      return;
     swap_status(status, by_status, (u32)(seq % g.num_slots), new_status);
   }
 }

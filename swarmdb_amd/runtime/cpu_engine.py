@@ -443,6 +443,10 @@ class CpuEngine(Engine):
 
     def set_status(self, seq: int, status: int) -> None:
         with self._lock:
+            # a seq never assigned names no message (k_set_status's guard;
+            # the CPU log never evicts, so that half is vacuous here)
+            if not 0 <= seq < self._count:
+                return
             prev = int(self._status[seq])
             if prev != status:
                 self._by_status[prev] -= 1
@@ -459,6 +463,9 @@ class CpuEngine(Engine):
     def set_statuses(self, seqs: np.ndarray, statuses: np.ndarray) -> None:
         with self._lock:
             idx = np.asarray(seqs, dtype=np.int64)
+            statuses = np.asarray(statuses)
+            live = (idx >= 0) & (idx < self._count)  # as set_status
+            idx, statuses = idx[live], statuses[live]
             old = self._status[idx]
             np.add.at(self._by_status, old, -1)
             np.add.at(self._by_status, statuses, 1)
