@@ -23,14 +23,13 @@ import numpy as np
 from ..core.config import QueueConfig
 from .engine import (
     BROADCAST,
-    FLAG_DERIVED_ID,
+    FETCH_DTYPE,
     NO_BITMAP,
     REC_DTYPE,
     ST_DELETED,
     ST_DELIVERED,
     ST_FAILED,
     ST_PENDING,
-    ST_PROCESSED,
     ST_READ,
     VIS_BITMAP,
     VIS_GROUP,
@@ -38,12 +37,6 @@ from .engine import (
 )
 
 _GROW = 2
-
-# fetch output layout: REC fields + status + seq (precomputed — building
-# it per call costs a dtype introspection per fetch)
-_FETCH_DTYPE = np.dtype(
-    REC_DTYPE.descr + [("status", np.uint8), ("seq", np.uint64)]
-)
 
 
 class _U64Ring:
@@ -302,18 +295,16 @@ class CpuEngine(Engine):
                 )
             return out.astype(np.uint64)
 
-    def receive_to_device(self, agent_idxs, max_per_agent,
-                          priority_order=False, max_payload=0, out=None):
-        # the base-class double, made one atomic step (dequeue + gather
-        # under the engine lock, as the GPU engine's single submission is)
-        with self._lock:
-            return super().receive_to_device(
-                agent_idxs, max_per_agent, priority_order, max_payload, out
-            )
+    # The device plane is the base class's doubles, each one atomic step
+    # under the engine lock, as the GPU engine's single submission is.
 
-    def ack_device(self, seqs, n=None, status=ST_PROCESSED):
+    def receive_to_device(self, *args, **kwargs):
         with self._lock:
-            super().ack_device(seqs, n, status)
+            return super().receive_to_device(*args, **kwargs)
+
+    def ack_device(self, *args, **kwargs):
+        with self._lock:
+            return super().ack_device(*args, **kwargs)
 
     def _park_failed(self, seqs: np.ndarray) -> np.ndarray:
         # the stored header of an error-lane record, as k_enqueue_meta
@@ -328,35 +319,23 @@ class CpuEngine(Engine):
             self._hdr["content_len"][failed] = 0
         return seqs
 
-    def enqueue_from_device(self, headers, payload, n=None):
+    def enqueue_from_device(self, *args, **kwargs):
         with self._lock:
-            return self._park_failed(
-                super().enqueue_from_device(headers, payload, n)
-            )
+            seqs = super().enqueue_from_device(*args, **kwargs)
+            return self._park_failed(seqs)
 
-    def reply_to_device(self, delivery, agent_idxs, payload, lengths,
-                        type_code, priority=None, flags=FLAG_DERIVED_ID,
-                        timestamp=None):
+    def reply_to_device(self, *args, **kwargs):
         with self._lock:
-            return self._park_failed(
-                super().reply_to_device(
-                    delivery, agent_idxs, payload, lengths, type_code,
-                    priority, flags, timestamp,
-                )
-            )
+            seqs = super().reply_to_device(*args, **kwargs)
+            return self._park_failed(seqs)
 
     def _context_window(self, lo, hi):
         # the log is dense on the CPU: views, no gather
         return self._hdr[lo:hi], self._status[lo:hi]
 
-    def context_to_device(self, delivery, agent_idxs, depth, lookback,
-                          type_code=None, max_payload=0, out=None, *,
-                          shared=False):
+    def context_to_device(self, *args, **kwargs):
         with self._lock:
-            return super().context_to_device(
-                delivery, agent_idxs, depth, lookback, type_code,
-                max_payload, out, shared=shared,
-            )
+            return super().context_to_device(*args, **kwargs)
 
     def peek_inbox(self, agent_idx: int) -> np.ndarray:
         with self._lock:
@@ -386,7 +365,7 @@ class CpuEngine(Engine):
                 bytes(mv[int(o) : int(o) + int(l)])
                 for o, l in zip(self._pay_off[seqs], self._pay_len[seqs])
             ]
-            out = np.zeros(len(seqs), dtype=_FETCH_DTYPE)
+            out = np.zeros(len(seqs), dtype=FETCH_DTYPE)
             for name in REC_DTYPE.names:
                 out[name] = hdr[name]
             out["status"] = status
@@ -400,7 +379,7 @@ class CpuEngine(Engine):
             seqs = np.asarray(seqs, dtype=np.int64)
             n = len(seqs)
             stride = int(self.cfg.slot_bytes)
-            out = np.zeros(n, dtype=_FETCH_DTYPE)
+            out = np.zeros(n, dtype=FETCH_DTYPE)
             h = self._hdr[seqs]
             for name in REC_DTYPE.names:
                 out[name] = h[name]

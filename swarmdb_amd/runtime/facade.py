@@ -47,6 +47,7 @@ from ..utils.hashing import partition_for
 from ..utils.tracing import tracer
 from .engine import (
     BROADCAST,
+    FETCH_DTYPE,
     FLAG_HAS_EXTRAS,
     FLAG_JSON_CONTENT,
     FLAG_OVERFLOW,
@@ -70,11 +71,6 @@ from .engine import (
 logger = logging.getLogger("swarmdb_amd")
 
 _STATUS_CODES = {n: i for i, n in enumerate(STATUS_NAMES)}
-
-# the row layout _reconstruct reads: what Engine.fetch returns
-_DELIVERY_ROW_DTYPE = np.dtype(
-    REC_DTYPE.descr + [("status", np.uint8), ("seq", np.uint64)]
-)
 
 
 def _status_code(status: Union[MessageStatus, str]) -> int:
@@ -680,6 +676,18 @@ class SwarmsDB:
         self._maybe_autosave()
         return seqs
 
+    def _polled_indices(self, delivery, agent_ids: List[str]) -> np.ndarray:
+        """The list ``delivery`` was polled with as uint32 agent indices,
+        or ValueError; the caller holds the lock."""
+        if len(agent_ids) != len(delivery.counts):
+            raise ValueError(
+                "agent_ids must be the list the delivery was polled with")
+        unknown = [a for a in agent_ids if a not in self.registered_agents]
+        if unknown:
+            raise ValueError(f"unregistered agents: {unknown}")
+        return np.array(
+            [self._agent_idx[a] for a in agent_ids], dtype=np.uint32)
+
     def reply_device(
         self,
         delivery: DeviceDelivery,
@@ -701,16 +709,7 @@ class SwarmsDB:
         anything is sent. Reply ids are the derived (rank, seq) ids, as
         for :meth:`send_batch`. Returns the replies' seqs, in row order."""
         with self._lock:
-            if len(agent_ids) != len(delivery.counts):
-                raise ValueError(
-                    "agent_ids must be the list the delivery was polled with"
-                )
-            unknown = [a for a in agent_ids if a not in self.registered_agents]
-            if unknown:
-                raise ValueError(f"unregistered agents: {unknown}")
-            idxs = np.array(
-                [self._agent_idx[a] for a in agent_ids], dtype=np.uint32
-            )
+            idxs = self._polled_indices(delivery, agent_ids)
         prio = None
         if priority is not None:
             prio = (priority if isinstance(priority, MessagePriority)
@@ -749,13 +748,7 @@ class SwarmsDB:
             n = len(self._llm_backends)
             if n == 0:
                 raise RuntimeError("no LLM backends registered")
-            if len(agent_ids) != len(delivery.counts):
-                raise ValueError(
-                    "agent_ids must be the list the delivery was polled with"
-                )
-            unknown = [a for a in agent_ids if a not in self.registered_agents]
-            if unknown:
-                raise ValueError(f"unregistered agents: {unknown}")
+            self._polled_indices(delivery, agent_ids)
             pinned = None
             if not self.llm_load_balancing:
                 assigned = self.metadata.get("llm_backends", {})
@@ -817,22 +810,24 @@ class SwarmsDB:
         length than the delivery's, raise ValueError. Nothing in the queue
         changes. ``out`` reuses the buffers of an earlier context."""
         with self._lock:
-            if len(agent_ids) != len(delivery.counts):
-                raise ValueError(
-                    "agent_ids must be the list the delivery was polled with"
-                )
-            unknown = [a for a in agent_ids if a not in self.registered_agents]
-            if unknown:
-                raise ValueError(f"unregistered agents: {unknown}")
-            idxs = np.array(
-                [self._agent_idx[a] for a in agent_ids], dtype=np.uint32
-            )
+            idxs = self._polled_indices(delivery, agent_ids)
         code = None if message_type is None else _type_code(message_type)
         with tracer.span("context_device", n=int(delivery.total)):
             return self.engine.context_to_device(
                 delivery, idxs, depth, lookback, code, max_payload, out,
                 shared=shared,
             )
+
+    def _delivery_rows(self, hdr: np.ndarray, seqs: np.ndarray) -> np.ndarray:
+        """The rows :meth:`_reconstruct` reads, from the REC_DTYPE records
+        and seqs of a host copy; statuses come from the engine."""
+        rows = np.zeros(len(hdr), dtype=FETCH_DTYPE)
+        for name in REC_DTYPE.names:
+            rows[name] = hdr[name]
+        rows["seq"] = seqs.astype(np.uint64)
+        if len(rows):
+            rows["status"] = self.engine.statuses(rows["seq"])
+        return rows
 
     def messages_from_context(
         self, ctx: DeviceContext, row: int
@@ -853,12 +848,7 @@ class SwarmsDB:
             raise ValueError(
                 "context was truncated by max_payload; it cannot be decoded"
             )
-        rows = np.zeros(n, dtype=_DELIVERY_ROW_DTYPE)
-        for name in REC_DTYPE.names:
-            rows[name] = hdr[name]
-        rows["seq"] = h.seqs[row, :n].astype(np.uint64)
-        if n:
-            rows["status"] = self.engine.statuses(rows["seq"])
+        rows = self._delivery_rows(hdr, h.seqs[row, :n])
         return [
             self._reconstruct(
                 rows[j], h.payload[row, j, : int(lens[j])].tobytes()
@@ -879,12 +869,7 @@ class SwarmsDB:
             raise ValueError(
                 "delivery was truncated by max_payload; it cannot be decoded"
             )
-        rows = np.zeros(h.total, dtype=_DELIVERY_ROW_DTYPE)
-        for name in REC_DTYPE.names:
-            rows[name] = h.headers[name]
-        rows["seq"] = h.seqs.astype(np.uint64)
-        if h.total:
-            rows["status"] = self.engine.statuses(rows["seq"])
+        rows = self._delivery_rows(h.headers, h.seqs)
         out: List[List[Message]] = []
         for b in range(len(h.counts)):
             lo, hi = int(h.offsets[b]), int(h.offsets[b + 1])

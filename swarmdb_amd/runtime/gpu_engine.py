@@ -19,28 +19,14 @@ from typing import Dict, List, Optional, Tuple
 import numpy as np
 
 from ..core.config import QueueConfig
-from .engine import (
-    FLAG_DERIVED_ID,
-    MAX_DISPATCH_BACKENDS,
-    REC_DTYPE,
-    ST_DELETED,
-    ST_PROCESSED,
-    DeviceContext,
-    DeviceDelivery,
-    DeviceDispatch,
-    Engine,
-    check_context_args,
-    check_context_out,
-    check_context_shared,
-    check_delivery_out,
-    check_dispatch_args,
-    check_dispatch_out,
-    check_reply_fields,
-    check_row_stride,
-    delivery_stride,
+from .device_plane import (
+    MAX_DISPATCH_BACKENDS, DeviceContext, DeviceDelivery, DeviceDispatch,
+    check_context_args, check_context_shared, check_dispatch_args,
+    check_reply_fields, check_row_stride, delivery_stride,
 )
-
-_FETCH_DTYPE = np.dtype(REC_DTYPE.descr + [("status", np.uint8), ("seq", np.uint64)])
+from .engine import (
+    FETCH_DTYPE, FLAG_DERIVED_ID, REC_DTYPE, ST_DELETED, ST_PROCESSED, Engine,
+)
 
 _NO_PINS = np.empty(0, dtype=np.int32)  # dispatch_delivery without pins
 
@@ -71,6 +57,7 @@ class GpuEngine(Engine):
         if torch is not None and torch.cuda.is_available():
             torch.cuda.init()
         self._torch_dev = None  # set by _torch_device on first use
+        self._out_plans: Dict[type, tuple] = {}  # see _check_out_tensors
         ext = _load_ext()
         if ext.device_count() == 0:  # pragma: no cover
             raise RuntimeError(
@@ -292,6 +279,7 @@ class GpuEngine(Engine):
             raise ValueError("max_per_agent must be >= 0")
         stride = delivery_stride(max_payload, self._slot_bytes)
         rows = na * K
+        p = {"na": na, "stride": stride, "rows": rows}
         # every refusal happens here or in the binding's own checks —
         # before the dequeue kernel moves a cursor
         if na > self.cfg.max_agents:
@@ -299,46 +287,26 @@ class GpuEngine(Engine):
         if rows > self.q.out_pool():
             raise ValueError("receive batch exceeds output pool")
         if out is not None:
-            check_delivery_out(out, na, rows, stride)
-            # placement only, not _check_device_tensor: its dtype, rank and
+            # placement only, not _check_out_tensors: its dtype, rank and
             # alignment tests cost 2-4 us on every tick that reuses `out`
-            for name in ("offsets", "seqs", "lengths", "agent_row",
-                         "headers", "payload"):
-                t = getattr(out, name)
-                if not (isinstance(t, torch.Tensor) and t.device == dev
-                        and t.is_contiguous()):
-                    raise ValueError(
-                        f"out.{name} must be a contiguous tensor on {dev}"
-                    )
-            offsets = out.offsets[: na + 1]
-            seqs, lengths, agent_row = out.seqs, out.lengths, out.agent_row
-            headers, payload = out.headers, out.payload
+            buf = DeviceDelivery.reuse(
+                out, p, self._check_out_placement, placement_only=True)
         else:
-            offsets = torch.zeros(na + 1, dtype=torch.int32, device=dev)
-            seqs = torch.empty(rows, dtype=torch.int64, device=dev)
-            lengths = torch.empty(rows, dtype=torch.int32, device=dev)
-            agent_row = torch.empty(rows, dtype=torch.int32, device=dev)
-            headers = torch.empty(
-                (rows, REC_DTYPE.itemsize), dtype=torch.uint8, device=dev
-            )
-            payload = torch.empty((rows, stride), dtype=torch.uint8, device=dev)
+            buf = DeviceDelivery.fresh(p, self._make_tensor)
         torch.cuda.current_stream(dev).synchronize()
         with self._lock:
             counts = self.q.receive_to_device(
                 agent_idxs, K, bool(priority_order), stride,
-                payload.data_ptr(), headers.data_ptr(), seqs.data_ptr(),
-                lengths.data_ptr(), agent_row.data_ptr(), offsets.data_ptr(),
-                int(payload.shape[0]),
+                buf["payload"].data_ptr(), buf["headers"].data_ptr(),
+                buf["seqs"].data_ptr(), buf["lengths"].data_ptr(),
+                buf["agent_row"].data_ptr(), buf["offsets"].data_ptr(),
+                int(buf["payload"].shape[0]),
             )
         counts = counts.astype(np.int64)
         total = int(counts.sum())
         if total:
             self._note_receive(agent_idxs, counts)
-        return DeviceDelivery(
-            counts=counts, offsets=offsets, seqs=seqs, lengths=lengths,
-            agent_row=agent_row, headers=headers, payload=payload,
-            stride=stride, total=total,
-        )
+        return DeviceDelivery(counts=counts, stride=stride, total=total, **buf)
 
     def ack_device(
         self, seqs, n: Optional[int] = None, status: int = ST_PROCESSED
@@ -380,6 +348,37 @@ class GpuEngine(Engine):
             raise ValueError(f"{name} must be contiguous")
         if t.data_ptr() % align:
             raise ValueError(f"{name} must be {align}-byte aligned")
+
+    # array maker and array-kind tests of the result tables (DeviceResult)
+    def _make_tensor(self, shape, f):
+        """A fresh tensor on the queue's GPU, zeroed where the table says."""
+        torch, dev = self._torch_device()
+        make = torch.zeros if f.gpu_zero else torch.empty
+        return make(shape, dtype=getattr(torch, f.dtype), device=dev)
+
+    def _check_out_tensors(self, cls, tensors) -> None:
+        """:meth:`_check_device_tensor` for every buffer of a ``cls``, its
+        arguments resolved once per class and its tests run in line: this
+        is on the tick path. A failing tensor is handed over for its message."""
+        torch, dev = self._torch_device()
+        plan = self._out_plans.get(cls)
+        if plan is None:
+            plan = self._out_plans[cls] = tuple(
+                ("out." + f.name, getattr(torch, f.dtype), f.ndim, f.align)
+                for f in cls.BUFFERS)
+        for (name, dtype, ndim, align), t in zip(plan, tensors):
+            if not (isinstance(t, torch.Tensor) and t.device == dev
+                    and t.dtype == dtype and t.dim() == ndim
+                    and t.is_contiguous() and t.data_ptr() % align == 0):
+                self._check_device_tensor(name, t, dtype, ndim, align)
+
+    def _check_out_placement(self, cls, tensors) -> None:
+        torch, dev = self._torch_device()
+        for f, t in zip(cls.BUFFERS, tensors):
+            if not (isinstance(t, torch.Tensor) and t.device == dev
+                    and t.is_contiguous()):
+                raise ValueError(
+                    f"out.{f.name} must be a contiguous tensor on {dev}")
 
     def _check_delivery_tensors(self, delivery: DeviceDelivery, total: int,
                                 need_seqs: bool) -> None:
@@ -504,11 +503,11 @@ class GpuEngine(Engine):
     # --- message store ---
 
     def _fetch(self, seqs: np.ndarray, keep) -> np.ndarray:
-        """Headers, statuses and seqs of ``seqs`` as one _FETCH_DTYPE
+        """Headers, statuses and seqs of ``seqs`` as one FETCH_DTYPE
         array, a chunk at a time; ``keep(a, b, hdr, pay_b)`` takes each
         chunk's payload rows (``slot_bytes`` apart in ``pay_b``)."""
         seqs = np.ascontiguousarray(seqs, dtype=np.uint64)
-        out = np.zeros(len(seqs), dtype=_FETCH_DTYPE)
+        out = np.zeros(len(seqs), dtype=FETCH_DTYPE)
         for a, b in self._chunks(len(seqs)):
             hdr_b, status, pay_b = self.q.fetch(seqs[a:b])
             hdr = np.frombuffer(hdr_b, dtype=REC_DTYPE, count=b - a)
@@ -753,36 +752,26 @@ class GpuEngine(Engine):
         if na > self.cfg.max_agents:
             raise ValueError("more polled agents than max_agents")
         self._check_delivery_tensors(delivery, total, need_seqs=False)
+        p = {"n_backends": nb, "rows": total}
         if out is not None:
-            check_dispatch_out(out, nb, total)
-            for name in ("backend", "order", "rank", "offsets"):
-                self._check_device_tensor(
-                    f"out.{name}", getattr(out, name), torch.int32, 1, 4)
-            self._check_device_tensor("out.added", out.added, torch.int64, 1, 8)
-            backend, order, rank = out.backend, out.order, out.rank
-            offsets, added = out.offsets, out.added
+            buf = DeviceDispatch.reuse(out, p, self._check_out_tensors)
         else:
-            rows = int(delivery.agent_row.shape[0])
-            backend = torch.empty(rows, dtype=torch.int32, device=dev)
-            order = torch.empty(rows, dtype=torch.int32, device=dev)
-            rank = torch.empty(rows, dtype=torch.int32, device=dev)
-            offsets = torch.empty(nb + 1, dtype=torch.int32, device=dev)
-            added = torch.empty(nb, dtype=torch.int64, device=dev)
+            p["rows"] = int(delivery.agent_row.shape[0])
+            buf = DeviceDispatch.fresh(p, self._make_tensor)
         torch.cuda.current_stream(dev).synchronize()
         with self._lock:
             counts = self.q.dispatch_from_device(
                 delivery.headers.data_ptr(), delivery.agent_row.data_ptr(),
                 total, pins if pins is not None else _NO_PINS,
                 pins is not None, nb, code, by_tokens,
-                backend.data_ptr(), rank.data_ptr(), order.data_ptr(),
-                offsets.data_ptr(), added.data_ptr(),
+                buf["backend"].data_ptr(), buf["rank"].data_ptr(),
+                buf["order"].data_ptr(), buf["offsets"].data_ptr(),
+                buf["added"].data_ptr(),
             )
         counts = np.asarray(counts, dtype=np.int64)
         return DeviceDispatch(
-            backend=backend, order=order, offsets=offsets, added=added,
-            counts=counts, rank=rank, n_backends=nb, total=total,
-            m=int(counts.sum()),
-        )
+            counts=counts, n_backends=nb, total=total, m=int(counts.sum()),
+            **buf)
 
     def release_dispatch(self, dispatch: DeviceDispatch) -> None:
         """k_release_loads over the dispatch's own ``added`` tensor, on
@@ -843,41 +832,24 @@ class GpuEngine(Engine):
         if group not in (0, ext.CONTEXT_GROUP, ext.CONTEXT_GROUP_WIDE):
             raise ValueError("group must be 0, 4 or 16")
         D = depth
+        p = {"depth": D, "stride": stride, "rows": total}
         if out is not None:
-            check_context_out(out, D, stride, total)
-            self._check_device_tensor("out.counts", out.counts, torch.int32, 1, 4)
-            self._check_device_tensor("out.seqs", out.seqs, torch.int64, 2, 8)
-            self._check_device_tensor(
-                "out.lengths", out.lengths, torch.int32, 2, 4)
-            self._check_device_tensor(
-                "out.headers", out.headers, torch.uint8, 3, 16)
-            self._check_device_tensor(
-                "out.payload", out.payload, torch.uint8, 3, 16)
-            counts, seqs, lengths = out.counts, out.seqs, out.lengths
-            headers, payload = out.headers, out.payload
+            buf = DeviceContext.reuse(out, p, self._check_out_tensors)
         else:
-            rows = int(delivery.agent_row.shape[0])
-            counts = torch.empty(rows, dtype=torch.int32, device=dev)
-            seqs = torch.empty((rows, D), dtype=torch.int64, device=dev)
-            lengths = torch.empty((rows, D), dtype=torch.int32, device=dev)
-            headers = torch.empty(
-                (rows, D, REC_DTYPE.itemsize), dtype=torch.uint8, device=dev)
-            payload = torch.empty(
-                (rows, D, stride), dtype=torch.uint8, device=dev)
+            p["rows"] = int(delivery.agent_row.shape[0])
+            buf = DeviceContext.fresh(p, self._make_tensor)
         if total:
             torch.cuda.current_stream(dev).synchronize()
             with self._lock:
                 self.q.context_to_device(
                     delivery.seqs.data_ptr(), delivery.agent_row.data_ptr(),
                     delivery.headers.data_ptr(), total, agents, D, lookback,
-                    code, stride, counts.data_ptr(), seqs.data_ptr(),
-                    lengths.data_ptr(), headers.data_ptr(),
-                    payload.data_ptr(), int(group), shared,
+                    code, stride, buf["counts"].data_ptr(),
+                    buf["seqs"].data_ptr(), buf["lengths"].data_ptr(),
+                    buf["headers"].data_ptr(), buf["payload"].data_ptr(),
+                    int(group), shared,
                 )
-        return DeviceContext(
-            counts=counts, seqs=seqs, lengths=lengths, headers=headers,
-            payload=payload, depth=D, stride=stride, total=total,
-        )
+        return DeviceContext(depth=D, stride=stride, total=total, **buf)
 
     # --- lifecycle ---
 
